@@ -12,6 +12,17 @@
             Setup (untimed, reported as `adaptation`): engine creation, set_position, the 400 tuning draws.
             Then W untimed post-warm-up steps, then R repeats of EXACTLY K timed steps, each between
             barrier + device sync; `value` is the MEDIAN repeat (all repeats are listed in `repeats`).
+            R is 1 unless --repeats or --full says otherwise, so that a plain run times exactly --steps steps.
+  plain run vs --full: a plain run does what the headline needs and no more — set-up, warm-up, the timed steps, --dump-outputs,
+            the line (metric, value, unit, ms_per_step, config, adaptation, ...).  --full adds everything below that takes work of its
+            own: 5 repeats (default), the roofline with its live counter passes, the box calibration, the other configurations, the
+            low-rank adaptation and the CPU baseline.
+  --dump-outputs DIR: after the timed steps, what the timed launch handed its caller in its LAST step, rank 0's chains: the draw's
+            positions (position.npy, [chains][dim]) and the fields of its statistics rows a NUTS draw defines (stats_<field>.npy,
+            [chains]; not the MCLMC-only energy_change / average_step_size nor divergence_energy_error, which hold NaN for "none"
+            and whose presence `diverging` carries), float64.
+            Inputs depend on the arguments only (seeded), so two builds can be compared file for file.  Above 60 MiB in all, a fixed
+            seeded sample of the chains (the same rows in every file; stats_chain.npy holds their ids).
   N GPUs  : one process per GPU (torch.distributed, RCCL backend); `python bench.py --gpus N` starts the N ranks itself
             (torch.distributed.run) when it is not already running under a launcher.  Chains shard with no data-path
             collective (global chain id = rank * 4096 + local id; results are invariant to the partition) => "weak"
@@ -35,7 +46,7 @@
             the shared rank-256 transformation, the matrix-core kernel) — each measured by this script in the same run (one untimed
             warm-up, one timed launch of --other-steps recorded draws, HIP-event kernel time) with its own roofline from live
             rocprofv3 --pmc passes: HBM (FETCH_SIZE / WRITE_SIZE) for K3 / K4, f64 MFMA (SQ_VALU_MFMA_BUSY_CYCLES) for K5.
-            The headline `value` stays K2.  --other-configs none skips them.
+            The headline `value` stays K2.  --other-configs none skips them.  (Roofline, low_rank_adaptation, other_configs: --full only.)
 The state is resident in HBM before the timed region (positions are uploaded in set_position; draws stay on the
 device), so `value` contains no PCIe traffic.
 """
@@ -68,7 +79,12 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=10)
-    p.add_argument("--repeats", type=int, default=5, help="timed repeats of K steps each; value = the median")
+    p.add_argument("--repeats", type=int, default=None, help="timed repeats of K steps each; value = the median (default 1, with --full 5)")
+    p.add_argument("--full", action="store_true",
+                   help="also the measurements beyond the headline: repeats, roofline and counter passes, box calibration, other configs, "
+                        "low-rank adaptation, CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's positions and statistics (rank 0's chains) as float64 DIR/<name>.npy")
     p.add_argument("--chains", type=int, default=4096, help="chains per GPU")
     p.add_argument("--dim", type=int, default=1024)
     p.add_argument("--num-tune", type=int, default=400)
@@ -92,7 +108,12 @@ def parse():
     p.add_argument("--config", default="k2", help="k2 (the headline line; default) | k4: BASELINE's 8-schools configuration, 65536 chains sharded over the "
                                                   "ranks (strong scaling), with --pooled the opt-in pooled adaptation: ONE RCCL all_gather per window")
     p.add_argument("--pooled", action="store_true", help="--config k4: warm up with the cross-chain pooled Welford reduction (nuts_rs_amd/pooled.py)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.dump_outputs and args.no_record:
+        p.error("--dump-outputs writes the recorded draws: drop --no-record")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -599,6 +620,30 @@ def low_rank_adaptation(seed):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+DUMP_BYTES = 60 << 20          # the data of --dump-outputs (the .npy headers stay within 64 MB beside it)
+# nm_draw_stats fields a NUTS draw leaves undefined: NaN stands for the reference's None (MclmcStats; DivergenceInfo of a draw that
+# did not diverge).  They are not dumped: everything that is holds a value.
+DUMP_SKIP_STATS = ("energy_change", "average_step_size", "divergence_energy_error")
+
+
+def dump_outputs(out_dir, d_pos_last, st_last):
+    """--dump-outputs: the positions [chains][dim] (a device tensor) and the statistics rows [chains] of the last timed step, as float64
+    DIR/position.npy and DIR/stats_<field>.npy (the fields not in DUMP_SKIP_STATS); above DUMP_BYTES a fixed seeded sample of the chains,
+    the same rows in every file."""
+    import torch
+    n_chains, dim = d_pos_last.shape
+    names = [f for f in st_last.dtype.names if f not in DUMP_SKIP_STATS]
+    rows = np.arange(n_chains)
+    per_chain = 8 * (dim + len(names))
+    if n_chains * per_chain > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n_chains, DUMP_BYTES // per_chain, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    pos = d_pos_last[torch.as_tensor(rows, device=d_pos_last.device)].cpu().numpy()
+    np.save(os.path.join(out_dir, "position.npy"), pos.astype(np.float64))
+    for f in names:
+        np.save(os.path.join(out_dir, f"stats_{f}.npy"), st_last[f][rows].astype(np.float64))
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` outside a launcher: start the N ranks (one per GPU) and relay rank 0's line."""
     import torch
@@ -671,6 +716,8 @@ def main_k4(args, N, torch, dist, rank, world, device_index, red_dev, barrier):
         g = [torch.zeros(len(mine), dtype=torch.float64, device=red_dev) for _ in range(world)]
         dist.all_gather(g, torch.tensor(mine, dtype=torch.float64, device=red_dev))
         per_rank = [[float(v) for v in t.tolist()] for t in g]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_pos[-1], np.frombuffer(d_st[-1].cpu().numpy().tobytes(), dtype=N.STATS_DTYPE))
     if rank == 0:
         rates = [sv * D / el for el, sv in reps]
         mid = int(np.argsort(rates)[len(rates) // 2])
@@ -810,51 +857,20 @@ def main():
     recorded_ok = None
     st_all = None
     if record and rank == 0:     # the last repeat's buffers hold real draws: finite positions, the right draw indices
-        st_all = np.frombuffer(d_st.cpu().numpy().tobytes(), dtype=N.STATS_DTYPE).reshape(args.steps, C_)
-        st_host = st_all[-1]
+        if args.full:            # (the roofline's bound model reads the statistics of every timed draw)
+            st_all = np.frombuffer(d_st.cpu().numpy().tobytes(), dtype=N.STATS_DTYPE).reshape(args.steps, C_)
+        st_host = np.frombuffer(d_st[-1].cpu().numpy().tobytes(), dtype=N.STATS_DTYPE)
         first_draw = args.num_tune + args.warmup + (R - 1) * args.steps
         recorded_ok = bool(torch.isfinite(d_pos[-1]).all().item()) and bool((st_host["draw"] == first_draw + args.steps - 1).all()) \
             and bool((st_host["n_steps"] > 0).all())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, d_pos[-1], st_host)
     if rank == 0:
         rates = [s_tot * D / el for el, s_tot, _, _ in reps]
         order = np.argsort(rates)
         mid = int(order[len(order) // 2])                       # the median repeat IS the reported measurement
         elapsed_max, steps_total, steps_local, kern_ms = reps[mid]
         value = rates[mid]
-        kern_s = kern_ms * 1e-3                                 # HIP events on the engine's own stream (nm_engine_get_counters)
-        algo_bytes = steps_local * D * ALGO_BYTES_PER_STEP_DIM
-        cal = calibration()
-        traffic = traffic_src = None
-        pmc_detail = {}
-        if world == 1 and args.pmc == "live":
-            got, why = pmc_live(args)
-            if got:
-                child_steps = (got.get("child", {}).get("fetch") or {}).get("steps") or steps_local
-                fetch_b = got["FETCH_SIZE"] * 1024.0 * cal["fetch_factor"]
-                write_b = got["WRITE_SIZE"] * 1024.0 * cal["write_factor"]
-                per_step_dim = (fetch_b + write_b) / (child_steps * D)
-                traffic = per_step_dim * steps_local * D     # the profiled launch's bytes per step x dim, at this launch's steps
-                traffic_src = "live rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload on this GPU"
-                pmc_detail = {"fetch_bytes": fetch_b, "write_bytes": write_b, "hbm_bytes_per_step_dim": per_step_dim,
-                              "profiled_launch_steps": child_steps, "calibration": cal}
-                if "SQ_WAVE_CYCLES" in got and got["SQ_WAVE_CYCLES"]:
-                    wc = got["SQ_WAVE_CYCLES"]
-                    pmc_detail["issue"] = {
-                        "note": "second bound: a wavefront's dependent chain (one wave per SIMD at 512 registers)",
-                        "wait_any_frac": got.get("SQ_WAIT_ANY", 0.0) / wc,
-                        "wait_inst_frac": got.get("SQ_WAIT_INST_ANY", 0.0) / wc,
-                        "active_inst_frac": got.get("SQ_ACTIVE_INST_ANY", 0.0) / wc,
-                        "valu_active_frac": got.get("SQ_ACTIVE_INST_VALU", 0.0) / wc,
-                        "valu_insts_per_leapfrog_wave": got.get("SQ_INSTS_VALU", 0.0) / max(1, child_steps),
-                        "salu_insts_per_leapfrog_wave": got.get("SQ_INSTS_SALU", 0.0) / max(1, child_steps)}
-                if got.get("skipped"):
-                    pmc_detail["skipped_passes"] = got["skipped"]
-            else:
-                pmc_detail = {"live_failed": why}
-        if traffic is None and args.pmc != "off":
-            traffic, traffic_src = pmc_profile(steps_local * D)
-        achieved = (traffic / kern_s / 1e9) if traffic else None
-        bm = (bound_model(st_all, D, kern_s, traffic) if st_all is not None else None) or {}
         out = {
             "metric": "leapfrog-steps*dims/sec at 4096 chains x dim 1024 (post-warm-up NUTS draws)",
             "value": value, "unit": "leapfrog-steps*dims/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -872,52 +888,87 @@ def main():
             "adaptation": {"value": tune_steps_total * D / t_tune_max, "unit": "leapfrog-steps*dims/s",
                            "draws": args.num_tune, "seconds": t_tune_max},
             "schema_version": SCHEMA_VERSION,
-            "roofline": {**(one_bound(bm["binding"], bm["terms_ms"], kern_s, bm.get("necessary_valu_instr"), (bm.get("hbm") or {}).get("necessary_bytes"))
-                            if bm.get("binding") else {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None}),
-                         # bound / achieved / peak / unit / frac describe ONE bound (schema 6; rounds 4 - 5 printed HBM GB/s beside the issue bound's frac);
-                         # what the kernel MOVED through HBM is `hbm_moved`
-                         "hbm_moved": {"achieved_GBps": achieved, "peak_GBps": HBM_PEAK_GBS, "frac_moved": (achieved / HBM_PEAK_GBS) if achieved else None},
-                         "binding": bm.get("binding"), "waste_ratio": (bm.get("hbm") or {}).get("moved_over_necessary"),
-                         "t_min_ms": bm.get("t_min_ms"), "t_kernel_ms": kern_s * 1e3,
-                         "frac_moved": (achieved / HBM_PEAK_GBS) if achieved else None,
-                         "frac_sec8d_model": algo_bytes / kern_s / 1e9 / HBM_PEAK_GBS,
-                         "frac_definition": "frac = achieved / peak of the BINDING bound = t_min / t_kernel with t_min = max(necessary HBM bytes / 8 TB/s, necessary f64 VALU instructions / "
-                                            "(1024 SIMDs x 2.4 GHz / 4)) — a bound: <= 1 and not raised by moving more bytes (bound_model has the "
-                                            "enumeration); waste_ratio = HBM bytes moved / necessary; frac_moved = moved bytes (PMC) / launch time / "
-                                            "8 TB/s = achieved / peak (a utilisation); frac_sec8d_model = 64 B x steps x dims / launch time / 8 TB/s "
-                                            "(SURVEY 8(d)'s streaming model; exceeds 1 because live points, sigma, mu never leave the CU)",
-                         "bound_model": bm,
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": KERNEL, "kernel_ms_per_launch": kern_ms, "launches": 1,
-                         "frac_of_measured_copy": (achieved / (cal.get("copy_GBps") or HBM_COPY_GBS)) if achieved else None,
-                         "measured_copy_GBps": cal.get("copy_GBps"), "measured_triad_GBps": cal.get("triad_GBps"),
-                         "algorithmic": {"bytes_per_step_dim": ALGO_BYTES_PER_STEP_DIM, "bytes_per_launch": algo_bytes,
-                                         "rate_GBps": algo_bytes / kern_s / 1e9,
-                                         "moved_over_algorithmic": (traffic / algo_bytes) if traffic else None,
-                                         "note": "SURVEY §8(d)'s streaming model; not a bound here: live points, sigma, mu "
-                                                 "stay in registers / LDS, HBM carries the tree's end points instead"},
-                         "pmc": pmc_detail},
         }
-        if world == 1:
-            out["calibration"] = box_calibration("k2", value)
-        if world == 1 and args.other_configs != "none":
-            batch.close()                                    # (K2's 1.5 GB of chain state and the record buffers go first)
-            batch = None
-            del d_pos, d_st
-            torch.cuda.empty_cache()
-            out["other_configs"] = other_configs(args)
-            try:
-                out["low_rank_adaptation"] = low_rank_adaptation(args.seed)
-            except Exception as e:  # noqa: BLE001  (the bench line must still be printed)
-                out["low_rank_adaptation"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
-            cores, cores_note = usable_cores()
-            try:
-                out["cpu_baseline"] = cpu_baseline(args, cores)
-                out["cpu_baseline"]["cores_note"] = cores_note
-            except Exception as e:   # the bench line must still be printed
-                out["cpu_baseline"] = {"value": None, "unit": "leapfrog-steps*dims/s", "cores": cores, "kind": "port",
-                                       "sample": f"failed: {e}"}
+        if args.full:
+            kern_s = kern_ms * 1e-3                                 # HIP events on the engine's own stream (nm_engine_get_counters)
+            algo_bytes = steps_local * D * ALGO_BYTES_PER_STEP_DIM
+            cal = calibration()
+            traffic = traffic_src = None
+            pmc_detail = {}
+            if world == 1 and args.pmc == "live":
+                got, why = pmc_live(args)
+                if got:
+                    child_steps = (got.get("child", {}).get("fetch") or {}).get("steps") or steps_local
+                    fetch_b = got["FETCH_SIZE"] * 1024.0 * cal["fetch_factor"]
+                    write_b = got["WRITE_SIZE"] * 1024.0 * cal["write_factor"]
+                    per_step_dim = (fetch_b + write_b) / (child_steps * D)
+                    traffic = per_step_dim * steps_local * D     # the profiled launch's bytes per step x dim, at this launch's steps
+                    traffic_src = "live rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload on this GPU"
+                    pmc_detail = {"fetch_bytes": fetch_b, "write_bytes": write_b, "hbm_bytes_per_step_dim": per_step_dim,
+                                  "profiled_launch_steps": child_steps, "calibration": cal}
+                    if "SQ_WAVE_CYCLES" in got and got["SQ_WAVE_CYCLES"]:
+                        wc = got["SQ_WAVE_CYCLES"]
+                        pmc_detail["issue"] = {
+                            "note": "second bound: a wavefront's dependent chain (one wave per SIMD at 512 registers)",
+                            "wait_any_frac": got.get("SQ_WAIT_ANY", 0.0) / wc,
+                            "wait_inst_frac": got.get("SQ_WAIT_INST_ANY", 0.0) / wc,
+                            "active_inst_frac": got.get("SQ_ACTIVE_INST_ANY", 0.0) / wc,
+                            "valu_active_frac": got.get("SQ_ACTIVE_INST_VALU", 0.0) / wc,
+                            "valu_insts_per_leapfrog_wave": got.get("SQ_INSTS_VALU", 0.0) / max(1, child_steps),
+                            "salu_insts_per_leapfrog_wave": got.get("SQ_INSTS_SALU", 0.0) / max(1, child_steps)}
+                    if got.get("skipped"):
+                        pmc_detail["skipped_passes"] = got["skipped"]
+                else:
+                    pmc_detail = {"live_failed": why}
+            if traffic is None and args.pmc != "off":
+                traffic, traffic_src = pmc_profile(steps_local * D)
+            achieved = (traffic / kern_s / 1e9) if traffic else None
+            bm = (bound_model(st_all, D, kern_s, traffic) if st_all is not None else None) or {}
+            out["roofline"] = {**(one_bound(bm["binding"], bm["terms_ms"], kern_s, bm.get("necessary_valu_instr"), (bm.get("hbm") or {}).get("necessary_bytes"))
+                                  if bm.get("binding") else {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None}),
+                               # bound / achieved / peak / unit / frac describe ONE bound (schema 6; rounds 4 - 5 printed HBM GB/s beside the issue bound's frac);
+                               # what the kernel MOVED through HBM is `hbm_moved`
+                               "hbm_moved": {"achieved_GBps": achieved, "peak_GBps": HBM_PEAK_GBS, "frac_moved": (achieved / HBM_PEAK_GBS) if achieved else None},
+                               "binding": bm.get("binding"), "waste_ratio": (bm.get("hbm") or {}).get("moved_over_necessary"),
+                               "t_min_ms": bm.get("t_min_ms"), "t_kernel_ms": kern_s * 1e3,
+                               "frac_moved": (achieved / HBM_PEAK_GBS) if achieved else None,
+                               "frac_sec8d_model": algo_bytes / kern_s / 1e9 / HBM_PEAK_GBS,
+                               "frac_definition": "frac = achieved / peak of the BINDING bound = t_min / t_kernel with t_min = max(necessary HBM bytes / 8 TB/s, necessary f64 VALU instructions / "
+                                                  "(1024 SIMDs x 2.4 GHz / 4)) — a bound: <= 1 and not raised by moving more bytes (bound_model has the "
+                                                  "enumeration); waste_ratio = HBM bytes moved / necessary; frac_moved = moved bytes (PMC) / launch time / "
+                                                  "8 TB/s = achieved / peak (a utilisation); frac_sec8d_model = 64 B x steps x dims / launch time / 8 TB/s "
+                                                  "(SURVEY 8(d)'s streaming model; exceeds 1 because live points, sigma, mu never leave the CU)",
+                               "bound_model": bm,
+                               "traffic": traffic, "traffic_source": traffic_src,
+                               "kernel": KERNEL, "kernel_ms_per_launch": kern_ms, "launches": 1,
+                               "frac_of_measured_copy": (achieved / (cal.get("copy_GBps") or HBM_COPY_GBS)) if achieved else None,
+                               "measured_copy_GBps": cal.get("copy_GBps"), "measured_triad_GBps": cal.get("triad_GBps"),
+                               "algorithmic": {"bytes_per_step_dim": ALGO_BYTES_PER_STEP_DIM, "bytes_per_launch": algo_bytes,
+                                               "rate_GBps": algo_bytes / kern_s / 1e9,
+                                               "moved_over_algorithmic": (traffic / algo_bytes) if traffic else None,
+                                               "note": "SURVEY §8(d)'s streaming model; not a bound here: live points, sigma, mu "
+                                                       "stay in registers / LDS, HBM carries the tree's end points instead"},
+                               "pmc": pmc_detail}
+            if world == 1:
+                out["calibration"] = box_calibration("k2", value)
+            if world == 1 and args.other_configs != "none":
+                batch.close()                                    # (K2's 1.5 GB of chain state and the record buffers go first)
+                batch = None
+                del d_pos, d_st
+                torch.cuda.empty_cache()
+                out["other_configs"] = other_configs(args)
+                try:
+                    out["low_rank_adaptation"] = low_rank_adaptation(args.seed)
+                except Exception as e:  # noqa: BLE001  (the bench line must still be printed)
+                    out["low_rank_adaptation"] = {"error": f"{type(e).__name__}: {e}"}
+            if world == 1 and not args.no_cpu_baseline:
+                cores, cores_note = usable_cores()
+                try:
+                    out["cpu_baseline"] = cpu_baseline(args, cores)
+                    out["cpu_baseline"]["cores_note"] = cores_note
+                except Exception as e:   # the bench line must still be printed
+                    out["cpu_baseline"] = {"value": None, "unit": "leapfrog-steps*dims/s", "cores": cores, "kind": "port",
+                                           "sample": f"failed: {e}"}
         print(json.dumps(out))
     if batch is not None:
         batch.close()

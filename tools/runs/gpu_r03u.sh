@@ -10,4 +10,4 @@ import json
 for l in open("$O/leaf_crossover.jsonl"):
     d=json.loads(l); print(d['logp'],d['dim'],d['chains'],'lane_chains',d.get('lane_chains'),'%.3g'%d['leapfrogs_per_s'],'lane',d.get('lane_launches'),'grp',d['group_launches'])
 PY
-timeout 600 python bench.py > $O/bench.json 2> $O/bench.err; head -c 600 $O/bench.json; echo
+timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err; head -c 600 $O/bench.json; echo

@@ -13,4 +13,4 @@ for L in failing repaired; do
 done
 cat $O/repro.txt
 cd $GRAFT_REPO_ROOT; unset NUTS_AMD_LIB
-NUTS_AMD_SELFTEST=0 timeout 600 python bench.py > $O/bench_head.txt 2>$O/bench_head.err; tail -c 600 $O/bench_head.txt
+NUTS_AMD_SELFTEST=0 timeout 600 python bench.py --full > $O/bench_head.txt 2>$O/bench_head.err; tail -c 600 $O/bench_head.txt
