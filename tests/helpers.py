@@ -1,4 +1,6 @@
 """Shared helpers for the parity tests: run the same configuration on the HIP engine and on the CPU oracle."""
+import ctypes as C
+
 import numpy as np
 
 import nuts_rs_amd as N
@@ -18,6 +20,17 @@ def oracle_settings(O, settings: N.DiagNutsSettings):
     return s
 
 
+def group_build_counters(b):
+    """(launches of the several-chains-per-wavefront kernels served by the one-wavefront-per-SIMD builds, the grid of those launches):
+    debug exports of the library, not part of the ABI, bound here as bench.py and tools/prof_*.py bind theirs."""
+    L = N.load_library()
+    out = []
+    for fn in (L.nm_debug_group_roomy_launches, L.nm_debug_group_grid):
+        fn.argtypes, fn.restype = [C.c_void_p], C.c_uint64
+        out.append(int(fn(b._h)))
+    return tuple(out)
+
+
 def run_engine(settings, logp, n_chains, x0, n_draws, chain_id_offset=0, dims_per_lane=0, waves_per_chain=0,
                lane_groups=0, grid_blocks=0, splits=(), lane_chains=0):
     """`splits`: draw counts at which the run is cut into separate launches; the pieces are concatenated."""
@@ -31,6 +44,7 @@ def run_engine(settings, logp, n_chains, x0, n_draws, chain_id_offset=0, dims_pe
         pos, st = np.concatenate([p for p, _ in parts]), np.concatenate([q for _, q in parts])
     extra = dict(status=status, threads_per_chain=b.threads_per_chain(), dims_per_lane=b.dims_per_lane(),
                  group_launches=b.group_launches(), lane_launches=b.lane_launches())
+    extra["group_roomy_launches"], extra["group_grid"] = group_build_counters(b)
     if pos is not None:
         sd, mu = b.mass_matrix()
         extra.update(stds=sd, mean=mu, step_sizes=b.step_sizes(), x=b.positions(), gx=b.gradients(),

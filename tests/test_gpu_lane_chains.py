@@ -88,7 +88,7 @@ def test_extra_doublings_beyond_two_lane_and_group_kernels(oracle, maxdepth, ext
 
 def test_lane_kernel_k4_many_chains_equals_the_other_kernels(oracle):
     """K4's shape at scale: 20000 chains of the 8-schools model.  The lane kernel, the 8-lanes-per-chain kernel and the wave kernel
-    give the same draws (whole run, every chain); sampled chains against the oracle; the state the host reads back agrees too."""
+    give the same draws (whole run, every chain); five sampled chains against the oracle, all 80 draws; the state the host reads back agrees too."""
     n = 20000
     s = N.DiagNutsSettings(num_chains=n, seed=9, num_tune=50)
     logp = N.LogpSpec.eight_schools()
@@ -103,6 +103,17 @@ def test_lane_kernel_k4_many_chains_equals_the_other_kernels(oracle):
         assert ((a == b) | ((a != a) & (b != b))).all(), f
     for k in ("stds", "mean", "step_sizes", "x", "gx"):
         assert (res["lane"][2][k].view(np.uint64) == res["group"][2][k].view(np.uint64)).all(), k
+    # 2500 wavefronts of 8 chains: more than 4 per CU, so the group run is served by the two-wavefronts-per-SIMD (non-roomy) builds
+    assert res["group"][2]["group_roomy_launches"] == 0 and res["lane"][2]["group_launches"] == 0
+    pos, st = res["lane"][0], res["lane"][1]
+    so = oracle_settings(oracle, s)
+    for c in (0, 4999, 8191, 13577, n - 1):
+        ch = oracle.Chain(so, oracle.LOGP_EIGHT_SCHOOLS, 10, logp.params, oracle.gpu_cfg(64), chain_id=c)
+        assert ch.set_position(x0[c]) == 0
+        for t in range(80):
+            p, q, rc = ch.draw()
+            assert rc == 0 and (p.view(np.uint64) == pos[t, c].view(np.uint64)).all(), (c, t)
+            assert q["n_steps"] == st["n_steps"][t, c] and q["step_size"] == st["step_size"][t, c]
 
 
 def test_lane_kernel_is_automatic_for_very_many_small_chains(oracle):
