@@ -21,12 +21,8 @@
 namespace nm {
 namespace grp {
 constexpr int GMAXDEPTH = 10;
-#ifndef NM_GROUP_OCC_TUNE
-#define NM_GROUP_OCC_TUNE 2  // ... and the warm-up kernel's (1 measured on K4's 8192-chain shard, where one wavefront per SIMD is resident anyway: see DESIGN §8)
-#endif
-#ifndef NM_GROUP_OCC
-#define NM_GROUP_OCC 2       // waves per SIMD the sampling kernel's register allocation leaves room for (3: spills, slower)
-#endif
+constexpr int NM_GROUP_OCC = 2;       // waves per SIMD the sampling kernel's register allocation leaves room for (3: spills, slower)
+constexpr int NM_GROUP_OCC_TUNE = 2;  // ... and the warm-up kernel's (1 measured on K4's 8192-chain shard, where one wavefront per SIMD is resident anyway: see DESIGN §8)
 // lanes per chain for a dim (0: no group form)
 __host__ __device__ inline int group_size(uint64_t dim) { return dim <= 16 ? 8 : dim <= 32 ? 16 : dim <= 64 ? 32 : 0; }
 }  // namespace grp

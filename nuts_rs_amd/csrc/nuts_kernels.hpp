@@ -29,18 +29,13 @@ namespace nm {
 
 constexpr int MAX_MAXDEPTH = 20;
 
-// LDS residency switches (tuning): which tree end points of the resident chain stay on the CU
-#ifndef NM_TRIM_FIRST
-#define NM_TRIM_FIRST 1   // first doubling / depth-1 top-level tests use the points still held in E
-#endif
+// LDS residency (the tile header sets 0): which tree end points of the resident chain stay on the CU
 #ifndef NM_LDS_L1
 #define NM_LDS_L1 1      // L[1]: last leaf of the pending level-1 sub-tree
 #endif
 // U-turn operand loops: at most this many unrolled iterations of operand loads may be in flight (a scheduling barrier
 // follows each group) — unbounded hoisting of the 6 operand streams costs ~190 VGPRs at DPL 16 and ends in scratch spills
-#ifndef NM_CHECK_GROUP
-#define NM_CHECK_GROUP 2
-#endif
+constexpr int NM_CHECK_GROUP = 2;
 #define NM_GROUP_BARRIER(m) do { if (((m) + 1) % NM_CHECK_GROUP == 0) __builtin_amdgcn_sched_barrier(0); } while (0)
 
 // ---------------------------------------------------------------------------------------------
@@ -76,76 +71,32 @@ __host__ __device__ inline int slot_R(int maxdepth, int i) { return num_sslots(m
 // (Computed once by the host into KParams::layout_md: reading both settings fields in ctx_begin changed the register allocation of the
 // 16-wavefront matrix-core kernel enough to break it — the last doubling of trees deeper than 6 stopped after one leaf)
 __host__ __device__ inline int layout_depth(const nm_settings& s) { return (int)(s.maxdepth + s.extra_doublings); }
-#ifndef NM_REG_EDGES
-#define NM_REG_EDGES 1            // the main tree's two end points live in registers (0: in the HBM scratch, rounds 1-4; bisecting builds)
-#endif
-#ifndef NM_EDGES_IN_ACC
-#define NM_EDGES_IN_ACC 0
-#endif
-#ifndef NM_LF_FMA_FORM
-#define NM_LF_FMA_FORM 0          // the fused leapfrog's two fused multiply-adds: 0 inline asm at the call sites of NM_X_ASM_SITES, 2 __builtin_fma everywhere
-#endif
-#ifndef NM_FUSED_LEAPFROG
-#define NM_FUSED_LEAPFROG 1        // 0: the leapfrog as three loops over the tile for every density (rounds 1-4; bisecting builds)
-#endif
-#ifndef NM_MERGE_MATH_ROUTINE
-#define NM_MERGE_MATH_ROUTINE 1   // 0: merge_weights through the general-purpose exp / ln_1p (rounds 1-4; bisecting builds)
-#endif
-#ifndef NM_BATCH_MERGES
-#define NM_BATCH_MERGES 1        // 0: every merge evaluated where the reference evaluates it (tuning / bisecting builds)
-#endif
-#ifndef NM_BATCH_IN_TILES
-#define NM_BATCH_IN_TILES 0
-#endif
-// Main-tree end points in registers (round 5).  The tree's left and right ends (z, v, g_z each) were scratch slots in HBM: written after
-// every doubling that is followed by another, read back by every top-level U-turn test (four tiles) and when the trajectory is extended on
-// the other side (three) — 30 of the ~64 tiles of 8 KiB a K2 draw moved, every read a round trip of a microsecond or two under load on the
-// wavefront's critical path.  A block of one wavefront per SIMD owns 512 registers per lane; two live points and two end points are
-// 12 tiles of 32 = 384 — which the register allocator does not manage without spilling to scratch memory (measured: 1088 B per lane), so
-// the end points' (z, v) — what every test reads — are registers and their g_z, read only when the trajectory is extended on the other
-// side, stays in its slot: 10 tiles.  Not for the register-capped tile / cluster builds.
-// Measured (profiles/r05f_*): (16 doubles, 1 wave) K2 2.02e11 -> 2.13e11, (2, 1) K3 +7 %; the register-capped tilings in between lose
-// ((8, 1) at two wavefronts per SIMD: -33 %, (4, 1): -7 %: the end points go to scratch memory) and keep the slots.
-template <int DPL, int W> constexpr bool reg_edges() { return bool(NM_REG_EDGES) & bool(NM_TRIM_FIRST) & !bool(NM_TILE_MODE) & !bool(NM_CLUSTER_MODE) & (W == 1) & (DPL == 16 || DPL == 2); }
-// timing experiment only (results are wrong): the U-turn tests of levels >= 2 and the top-level test read registers instead of their scratch slots
-#ifdef NM_X_NO_TEST_LOADS
-#define NM_TLD(r, so, m, alt) make_double2((alt).a[2 * (m)], (alt).a[2 * (m) + 1])
-#else
-#define NM_TLD(r, so, m, alt) C.ld2(r, so, m)
-#endif
-// Round 6 ("NOG" + "FD", the (16 doubles, 1 wavefront) tiling with an element-wise density and the diagonal transformation: K2).  The launch is bound by the
-// bytes the tree's end points move (21 B per step x dim against 3.7 necessary; every phase that touches memory stalls), so:
-//   NOG  a point is (z, v): its transformed gradient g_z is NOT kept.  For an element-wise density g_z is three operations per element away from z
-//        (x = sigma z + mu, g_x = density'(x), g_z = sigma g_x — the very operations that produced it, hence the same bits), so the leapfrog
-//        recomputes the start point's g_z on the fly (+4 instructions per element pair) instead of holding two more tiles of 32 registers and an
-//        HBM slot per main-tree edge.  The one gradient that is NOT a function of its z — the trajectory's initial point, whose z a
-//        re-whitening may have recomputed from x (transformed_hamiltonian.rs:687-736, diagonal.rs:210-221) — is streamed from its slot P_GZ.
-//   FD   the 64 registers that frees hold (z, v) of the FIRST leaf of the doubling in progress (F[depth]): the operand of every level-k test of
-//        a sub-tree that starts at leaf 0 and of the top-level test's third pair (src/nuts.rs:143-161) — written once and read two or three
-//        times per doubling before, now never in memory: the top-level tests read registers only.
-#ifndef NM_NOG
-#define NM_NOG 1
-#endif
-#ifndef NM_NOG_82
-#define NM_NOG_82 0   // the gradient-free points on the (8 doubles, 2 wavefronts) tiling too (measured: profiles/r06s_*)
-#endif
-#ifndef NM_TEST_CHUNK
-#define NM_TEST_CHUNK 4      // (16-doubles tiling) iterations the level-k / top-level U-turn tests request their slots' rows ahead: measured 0 / 2 / 4 / 8 (profiles/r06u_*)
-#endif
-#ifndef NM_TEST_CHUNK3_MAX
-#define NM_TEST_CHUNK3_MAX 2
-#endif
-#ifndef NM_FD
-#define NM_FD 0      // measured (profiles/r06n_k2_nog_variants.txt): the 64 registers cost more in spills than the loads they save
-#endif
-#ifndef NM_GTILE
-#define NM_GTILE 1     // 1: one shared gradient tile instead of recomputing the start point's g_z in every leapfrog (32 registers for 64 instructions per leapfrog)
-#endif
+// The one-chain-per-block kernels of a plain unit: the matrix-core (tile) and several-blocks-per-chain (cluster) units are register-capped
+// and keep the forms of rounds 1-4 throughout.
+constexpr bool plain_unit = !NM_TILE_MODE && !NM_CLUSTER_MODE;
+// Main-tree end points in registers (round 5): the (z, v) of the tree's left and right ends — what every top-level U-turn test reads — are
+// registers; their g_z, read only when the trajectory is extended on the other side, stays in its scratch slot.  For the tilings whose
+// register allocation has the room: (16 doubles, 1 wave) K2 2.02e11 -> 2.13e11, (2, 1) K3 +7 %; the register-capped tilings in between lose
+// ((8, 1): -33 %, (4, 1): -7 %: the end points go to scratch memory) and keep the slots (profiles/r05f_*).
+template <int DPL, int W> constexpr bool reg_edges() { return plain_unit && W == 1 && (DPL == 16 || DPL == 2); }
+// Batched merges (resolve_chunk): the one-wavefront tilings up to this width evaluate a doubling's merges together and keep a ring of the
+// last NM_RING leaves behind the tree's other scratch slots.  ONE predicate for the kernels and for the host's scratch layout.
+constexpr int NM_BATCH_MAX_DPL = 4;
+__host__ __device__ constexpr bool batched_merges(int dpl, int w, bool plain) { return plain && w == 1 && dpl <= NM_BATCH_MAX_DPL; }
+template <int DPL, int W> constexpr bool batched_merges() { return batched_merges(DPL, W, plain_unit); }
+// Gradient-free points (round 6, "NOG": the (16 doubles, 1 wavefront) tiling with an element-wise density and the diagonal transformation: K2).
+// The launch is bound by the bytes the tree's end points move, so a point is (z, v): its transformed gradient g_z is NOT kept.
+// For an element-wise density g_z is three operations per element away from z (x = sigma z + mu, g_x = density'(x), g_z = sigma g_x — the
+// very operations that produced it, hence the same bits); one shared gradient tile carries it from a leapfrog to the next.  The one gradient
+// that is NOT a function of its z — the trajectory's initial point, whose z a re-whitening may have recomputed from x
+// (transformed_hamiltonian.rs:687-736, diagonal.rs:210-221) — is streamed from its slot P_GZ.
+// Tried and dropped: the same on the (8, 2) tiling (profiles/r06s_*); recomputing the start point's g_z in every leapfrog instead of the shared
+// tile (profiles/r06n_k2_nog_variants.txt).
 template <int DPL, int W, class Dens> constexpr bool nog_mode();
-#ifndef NM_BATCH_MAX_DPL
-#define NM_BATCH_MAX_DPL 4      // the widest one-wavefront tiling with the batched merges (resolve_chunk); the host's scratch layout follows it
-#endif
-template <int DPL, int W> constexpr bool batched_merges() { return NM_BATCH_MERGES && DPL <= NM_BATCH_MAX_DPL && W == 1 && (!NM_TILE_MODE || NM_BATCH_IN_TILES) && !NM_CLUSTER_MODE; }
+// (16-doubles tiling) iterations the level-k / top-level U-turn tests request their slots' rows ahead: measured 0 / 2 / 4 / 8 (profiles/r06u_*);
+// the top-level test has six loads per iteration and looks at most NM_TEST_CHUNK3_MAX ahead
+constexpr int NM_TEST_CHUNK = 4;
+constexpr int NM_TEST_CHUNK3_MAX = 2;
 
 // Per-chain scalars (everything of NutsChain / GlobalStrategy / stepsize::Strategy / DualAverage that is not a vector)
 struct ChainScalars {
@@ -279,39 +230,15 @@ NM_DEV void store_tile(const Tile<DPL>& t, double* base) {
 #pragma unroll
     for (int m = 0; m < DPL / 2; ++m) p[m * 64 * W] = make_double2(t.a[2 * m], t.a[2 * m + 1]);
 }
-// element index held in register k of this thread
-// Where the end points live.  Plain values: the allocator keeps them in the accumulation registers of the (16, 1) kernel (all 512
-// registers of its SIMD) at ~150 more vector instructions per leapfrog.  Placing them there BY HAND (NM_EDGES_IN_ACC = 1: v_accvgpr_write /
-// read, one per 32 bits, a write per doubling, a read per test) was built and is worse: the 128 accumulation registers it pins are the
-// allocator's spill space, and what no longer fits goes to scratch memory (544 B per lane against 384).
-template <int DPL, bool ACC> struct EdgeTile;
-template <int DPL> struct EdgeTile<DPL, false> {
+// Where the register end points live (reg_edges).  Plain values: the allocator keeps them in the accumulation registers of the (16, 1) kernel.
+// Placing them there by hand (v_accvgpr_write / read) was built and is worse: 544 B of scratch per lane against 384.
+template <int DPL> struct EdgeTile {
     Tile<DPL> t;
     NM_DEV void put(const Tile<DPL>& s) { t = s; }
     NM_DEV void get(Tile<DPL>& d) const { d = t; }
     NM_DEV double2 pair(int m) const { return make_double2(t.a[2 * m], t.a[2 * m + 1]); }
 };
-template <int DPL> struct EdgeTile<DPL, true> {
-    int w[2 * DPL];
-    NM_DEV void put(const Tile<DPL>& s) {
-#pragma unroll
-        for (int k = 0; k < DPL; ++k) {
-            asm("v_accvgpr_write_b32 %0, %1" : "=a"(w[2 * k]) : "v"(__double2loint(s.a[k])));
-            asm("v_accvgpr_write_b32 %0, %1" : "=a"(w[2 * k + 1]) : "v"(__double2hiint(s.a[k])));
-        }
-    }
-    NM_DEV double at(int k) const {
-        int lo, hi;
-        asm("v_accvgpr_read_b32 %0, %1" : "=v"(lo) : "a"(w[2 * k]));
-        asm("v_accvgpr_read_b32 %0, %1" : "=v"(hi) : "a"(w[2 * k + 1]));
-        return __hiloint2double(hi, lo);
-    }
-    NM_DEV void get(Tile<DPL>& d) const {
-#pragma unroll
-        for (int k = 0; k < DPL; ++k) d.a[k] = at(k);
-    }
-    NM_DEV double2 pair(int m) const { return make_double2(at(2 * m), at(2 * m + 1)); }
-};
+// element index held in register k of this thread
 template <int W>
 NM_DEV int elem_index(int k) { return 2 * ((k >> 1) * 64 * W + tid()) + (k & 1); }
 
@@ -354,28 +281,11 @@ NM_DEV double2 buf_load2(rsrc_t r, int voff, int soff) {
     return make_double2(__hiloint2double((int)q.y, (int)q.x), __hiloint2double((int)q.w, (int)q.z));
 }
 // cache-policy bits of the raw buffer intrinsics on gfx940+: sc0 = 1, nt = 2, sc1 = 16
-#ifndef NM_NT_STORES
-#define NM_NT_STORES 1
-#endif
-constexpr int NM_AUX_NT = NM_NT_STORES ? 2 : 0;
-// Round 6: the one-wavefront 16-doubles tiling (K2) stores its candidates / per-draw state with the default policy: a lone wavefront waits for its
-// stores wherever the next s_waitcnt vmcnt happens to be (loads and stores share the counter), and a streaming store is acknowledged later than a
-// write-back one (measured, profiles/r06n_k2_nog_variants.txt: 2.10 -> 2.15e11 on the round-5 kernel, 2.24 -> 2.27e11 with gradient-free points).
-#ifndef NM_NT_MAX_DPL
-#define NM_NT_MAX_DPL 8
-#endif
-template <int DPL, int W> constexpr int aux_nt() { return (NM_NT_STORES && (DPL <= NM_NT_MAX_DPL || W > 1)) ? 2 : 0; }
-// Output rows of a draw: plain masked 8-byte stores (0), a per-row buffer descriptor with 16-byte stores for every vector output (1) or for the
-// position row only (2), and the cache policy of those stores.  Measured on K2 with every draw recorded (tools/gpu_wrb.sh,
-// profiles/r04zz_write_row_variants.txt): 0: 75.8 ms per 200 draws, 1: 73.4, 2: 72.4, 2 + non-temporal: 72.1 (without recording: 71 - 72 ms in
-// every form) — the position row is the one output every caller takes; the kernel is at its register cap and the form that touches the least
-// code wins.
-#ifndef NM_WRITE_ROW_BUF
-#define NM_WRITE_ROW_BUF 2
-#endif
-#ifndef NM_ROW_AUX
-#define NM_ROW_AUX 2
-#endif
+// Scratch and per-draw state are stored non-temporal (nt), except on the one-wavefront 16-doubles tiling (K2): a lone wavefront waits for its
+// stores wherever the next s_waitcnt vmcnt happens to be (loads and stores share the counter), and a streaming store is acknowledged later
+// than a write-back one (profiles/r06n_k2_nog_variants.txt: 2.10 -> 2.15e11 on the round-5 kernel, 2.24 -> 2.27e11 with gradient-free points).
+constexpr int NM_NT_MAX_DPL = 8;
+template <int DPL, int W> constexpr int aux_nt() { return (DPL <= NM_NT_MAX_DPL || W > 1) ? 2 : 0; }
 // The data registers of a 128-bit buffer store must not be overwritten right behind it.  LLVM's hazard recogniser knows this
 // hazard ("VMEM store of more than 64 bits, then a VALU write of its data VGPRs": 1 wait state) but exempts MUBUF stores whose
 // soffset is an SGPR — the addressing used here — and gfx950 does show it: `buffer_store_dwordx4 v[4:7], .., s8 offen` directly
@@ -772,8 +682,7 @@ template <class D> struct kin_trait<LrWrap<D>> { static constexpr bool value = t
 template <class D, class = void> struct tile_trait { static constexpr bool value = false; };
 template <class D> struct tile_trait<D, typename std::enable_if<D::kTile>::type> { static constexpr bool value = true; };
 template <int DPL, int W, class Dens> constexpr bool nog_mode() {
-    return bool(NM_NOG) && ((DPL == 16 && W == 1) || (bool(NM_NOG_82) && DPL == 8 && W == 2)) && bool(NM_TRIM_FIRST) && !bool(NM_TILE_MODE) && !bool(NM_CLUSTER_MODE) && bool(NM_FUSED_LEAPFROG) && !batched_merges<DPL, W>() &&
-           elementwise_trait<Dens>::value && !lr_trait<Dens>::value && !kin_trait<Dens>::value && !tile_trait<Dens>::value;
+    return plain_unit && DPL == 16 && W == 1 && elementwise_trait<Dens>::value && !lr_trait<Dens>::value && !kin_trait<Dens>::value && !tile_trait<Dens>::value;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -896,16 +805,13 @@ struct ChainCtx {
 #else
 #define NM_STAT_WRITER(C) (tid() == 0)
 #endif
+constexpr int NM_PACKED_MAX_DPL = 4;      // the widest tiling whose every sum is packed
 template <int DPL, int W, class Dens>
 NM_DEV void ctx_begin(ChainCtx<DPL, W, Dens>& C, BlockShared<DPL, W, Dens>& sh, uint64_t chain, uint64_t wave) {
-#ifndef NM_PACKED_MAX_DPL
-#define NM_PACKED_MAX_DPL 4
-#endif
-#ifndef NM_PACKED_TESTS_16
-#define NM_PACKED_TESTS_16 1     // the six sums of a level-k / top-level test through one transposed butterfly on the 16-doubles tiling too (2.48 -> 2.555e11: profiles/r06n_*)
-#endif
-    C.red.packed_tests = bool(NM_PACKED_TESTS_16) && DPL == 16 && W == 1 && !NM_TILE_MODE && !NM_CLUSTER_MODE;
-    C.red.packed = DPL <= NM_PACKED_MAX_DPL && !NM_TILE_MODE;        // (dev_math.hpp Reducer::packed: per tiling, from the measurements of round 5)
+    // dev_math.hpp Reducer: every sum of the small tilings goes through the transposed butterfly (round 5); the 16-doubles tiling sends only the
+    // sums of its U-turn tests and of the leapfrog through it (2.48 -> 2.555e11: profiles/r06n_*)
+    C.red.packed_tests = plain_unit && DPL == 16 && W == 1;
+    C.red.packed = DPL <= NM_PACKED_MAX_DPL && !NM_TILE_MODE;
     const KParams& P = C.P;
     C.dim = (int)P.dim; C.gdim = (int)P.dim; C.goff = 0;
 #if NM_CLUSTER_MODE
@@ -1208,23 +1114,18 @@ NM_DEV void leapfrog_kin(ChainCtx<DPL, W, Dens>& C, const Pt<DPL>& s, Pt<DPL>& o
 // One leapfrog, registers to registers (reference transformed_hamiltonian.rs:524-615 + diagonal.rs:196-209, :248-265):
 //   v½ = fma(ε/2, g_z, v); z' = fma(ε, v½, z); x' = z'·σ + μ; (logp, g_x) = density(x'); g_z' = g_x·σ;
 //   v' = fma(ε/2, g_z', v½); KE' = ½ Σ fma(v', v', ·)
-#ifndef NM_X_ASM_SITES
-#define NM_X_ASM_SITES 4          // call sites whose fused leapfrog uses the inline-asm form of its two fused multiply-adds: bit 0 MCLMC (x_out / gx_out), 1 the
-                                  // step-size search, 2 the tree.  Tree only: it is where the instruction pays (K2 +5 %: profiles/r05u), and every failing
-                                  // build of DESIGN §22's fourth incident had the asm form at the MCLMC site (never executed by the failing runs)
-#endif
+// SITE: the call site — 0 MCLMC (x_out / gx_out), 1 the step-size search, 2 the tree.  Only the tree's fused leapfrog spells its two fused
+// multiply-adds as inline asm: it is where the instruction pays (K2 +5 %: profiles/r05u), and every failing build of DESIGN §22's fourth
+// incident had the asm form at the MCLMC site.
 // GMODE (round 6, nog_mode): where the start point's g_z comes from — 0: its tile s.g; 1: recomputed from s.z (element-wise densities: the operations that
 // produced it); 2: streamed from the slot `gsrc` (the trajectory's initial point: P_GZ).  With GMODE != 0 neither s.g nor o.g is touched.
 template <int DPL, int W, class Dens, int SITE = 0, int GMODE = 0>
 NM_DEV void leapfrog(ChainCtx<DPL, W, Dens>& C, const Pt<DPL>& s, Pt<DPL>& o, double epsilon, Tile<DPL>* x_out, Tile<DPL>* gx_out,
                      typename ChainCtx<DPL, W, Dens>::SlotRef gsrc = typename ChainCtx<DPL, W, Dens>::SlotRef{}, Tile<DPL>* gshared = nullptr) {
-    // GMODE 3 (NM_GTILE): ONE gradient tile shared by the chain of leapfrogs — *gshared holds g_z of the point the previous leapfrog produced (= this one's
+    // GMODE 3: ONE gradient tile shared by the chain of leapfrogs — *gshared holds g_z of the point the previous leapfrog produced (= this one's
     // start point), is read element by element and overwritten with the end point's; modes 1 / 2 fill it when the chain of leapfrogs restarts elsewhere.
-    static_assert(GMODE == 0 || (elementwise_trait<Dens>::value && !lr_trait<Dens>::value && !kin_trait<Dens>::value && NM_FUSED_LEAPFROG && !NM_CLUSTER_MODE && !NM_TILE_MODE),
+    static_assert(GMODE == 0 || (elementwise_trait<Dens>::value && !lr_trait<Dens>::value && !kin_trait<Dens>::value && plain_unit),
                   "the gradient-free point needs the fused element-wise leapfrog");
-#ifdef NM_X_NO_LEAPFROG           // timing experiment only: the tree without its integrator
-    if (!x_out && !gx_out) { o.z = s.z; o.v = s.v; o.g = s.g; o.logp = s.logp + epsilon * 1e-6; o.ke = s.ke; return; }
-#endif
     if constexpr (kin_trait<Dens>::value) {
         if (C.sc.kin != NM_TRAJ_EUCLIDEAN) { leapfrog_kin(C, s, o, epsilon, x_out, gx_out); return; }
     }
@@ -1255,8 +1156,7 @@ NM_DEV void leapfrog(ChainCtx<DPL, W, Dens>& C, const Pt<DPL>& s, Pt<DPL>& o, do
     }
     const double2* sg2 = C.tptr(C.lsig);
     const double2* mu2 = C.tptr(C.lmu);
-#if NM_FUSED_LEAPFROG
-    if constexpr (elementwise_trait<Dens>::value && !NM_CLUSTER_MODE && !NM_TILE_MODE) {
+    if constexpr (elementwise_trait<Dens>::value && plain_unit) {
         // Element-wise densities: everything the step does to element k — half kick, drift, x = sigma z + mu, the density's gradient
         // element and logp term, g_z = sigma g_x, second half kick, v^2 — depends on element k alone; only the two sums couple the
         // elements, and nothing reads them before the end.  ONE pass, element pair by element pair, instead of three loops over the
@@ -1295,7 +1195,7 @@ NM_DEV void leapfrog(ChainCtx<DPL, W, Dens>& C, const Pt<DPL>& s, Pt<DPL>& o, do
                     // (v_fma_f64 spelled out: the source point's v and z stay live, and the compiler's two-address form — v_mov_b64 + v_fmac_f64 —
                     // costs an instruction more per fma; the same IEEE fused multiply-add)
                     double vh, zk;
-                    if constexpr (NM_LF_FMA_FORM == 0 && ((NM_X_ASM_SITES >> SITE) & 1)) {
+                    if constexpr (SITE == 2) {
                         asm("v_fma_f64 %0, %1, %2, %3" : "=v"(vh) : "v"(half), "v"(gsk), "v"(s.v.a[k]));
                         asm("v_fma_f64 %0, %1, %2, %3" : "=v"(zk) : "v"(epsilon), "v"(vh), "v"(s.z.a[k]));
                     } else {
@@ -1310,7 +1210,7 @@ NM_DEV void leapfrog(ChainCtx<DPL, W, Dens>& C, const Pt<DPL>& s, Pt<DPL>& o, do
                     acc = acc + term;
                     const double gk = gxk * sgk;
                     if constexpr (GMODE == 0) o.g.a[k] = gk;
-                    else if constexpr (NM_GTILE != 0) gshared->a[k] = gk;
+                    else gshared->a[k] = gk;
                     const double vk = __builtin_fma(half, gk, vh);
                     o.v.a[k] = vk;
                     kacc = __builtin_fma(vk, vk, kacc);
@@ -1326,7 +1226,7 @@ NM_DEV void leapfrog(ChainCtx<DPL, W, Dens>& C, const Pt<DPL>& s, Pt<DPL>& o, do
         o.ke = 0.5 * kacc;
         return;
     }
-#endif
+    // every other density, and the tile / cluster units: three loops over the tile
 #pragma unroll
     for (int m = 0; m < DPL / 2; ++m) {
         const double2 sg = sg2[m * 64 * W], mm = mu2[m * 64 * W];
@@ -1954,12 +1854,7 @@ enum TreeStop { STOP_NONE = 0, STOP_TURNING = 1, STOP_DIVERGING = 2, STOP_FATAL 
 // multinomial merge weights (reference merge_into, src/nuts.rs:172-207).  Returns take_B.
 template <int DPL, int W, class Dens>
 NM_DEV bool merge_weights(ChainCtx<DPL, W, Dens>& C, double a_log_size, double b_log_size, bool is_main, double& total, bool& fatal) {
-#ifdef NM_X_NO_MERGE_MATH      // timing experiment only (results are wrong): what do the merges' special functions + Bernoulli cost?
-    total = (a_log_size > b_log_size ? a_log_size : b_log_size) + 0.5; (void)is_main; (void)fatal;
-    return false;
-#endif
     NM_MARK(C, 13)
-#if NM_MERGE_MATH_ROUTINE
     // the whole of merge_into's arithmetic in one branch-free routine (dev_math.hpp merge_math).  The chain's next u64 is read here and
     // consumed only if the routine says random_bool drew it; refilling the word cache early changes nothing (it is a window onto the stream).
     if (!C.rng.has(2)) C.rng.refill();
@@ -1971,18 +1866,6 @@ NM_DEV bool merge_weights(ChainCtx<DPL, W, Dens>& C, double a_log_size, double b
     NM_MARK(C, 29)
     if (mf & 4u) fatal = true;
     return (mf & 1u) != 0;
-#else
-    total = logaddexp(a_log_size, b_log_size);
-    NM_MARK(C, 14)
-    const double self_log_size = is_main ? a_log_size : total;
-    if (b_log_size >= self_log_size) return true;
-    const double p_ = uexp(b_log_size - self_log_size);
-    NM_MARK(C, 15)
-    int b = C.rng.random_bool(p_);
-    NM_MARK(C, 29)
-    if (b < 0) { fatal = true; return false; }
-    return b == 1;
-#endif
 }
 
 struct DrawResult {
@@ -2155,12 +2038,16 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
     Pt<DPL> E, O;
     constexpr bool RE = reg_edges<DPL, W>();
     constexpr bool NOG = nog_mode<DPL, W, Dens>();       // points are (z, v): no g_z tile (see nog_mode)
-    constexpr bool FD = NOG && bool(NM_FD);                // the first leaf of the doubling in progress lives in FDz / FDv
-    constexpr int TCH = (DPL == 16 && W == 1 && !batched_merges<DPL, W>()) ? NM_TEST_CHUNK : 0;     // iterations a U-turn test requests its slots' rows ahead (16-doubles tiling)
-    [[maybe_unused]] Tile<DPL> Gsh;                        // NM_GTILE: g_z of the point the last leapfrog produced
-    [[maybe_unused]] Tile<DPL>* const gsh = NM_GTILE ? &Gsh : nullptr;
+    // FD: the first leaf of the doubling in progress (F[depth]) in the 64 registers NOG frees (FDz / FDv) instead of its scratch slot.  Measured
+    // and lost (profiles/r06n_k2_nog_variants.txt: the registers cost more in spills than the loads they save); the arm is still here, fixed off,
+    // because the closure of `level_rows` below captures FDz / FDv: without them the compiler allocates the registers of every kernel that
+    // takes the unbatched path differently (profiles/r07_switch_retirement_asm_identity.txt).  Removing it is a change of generated code.
+    constexpr bool FD = false;
+    constexpr int TCH = (DPL == 16 && W == 1) ? NM_TEST_CHUNK : 0;     // iterations a U-turn test requests its slots' rows ahead (16-doubles tiling)
+    [[maybe_unused]] Tile<DPL> Gsh;                        // NOG: g_z of the point the last leapfrog produced (leapfrog's GMODE 3)
+    [[maybe_unused]] Tile<DPL>* const gsh = &Gsh;
     [[maybe_unused]] Tile<DPL> FDz, FDv;
-    [[maybe_unused]] EdgeTile<DPL, NM_EDGES_IN_ACC != 0> MLz, MLv, MRz, MRv;   // RE: (z, v) of the main tree's left / right end point; their g_z (read only when the
+    [[maybe_unused]] EdgeTile<DPL> MLz, MLv, MRz, MRv;     // RE: (z, v) of the main tree's left / right end point; their g_z (read only when the
                                                           // trajectory is extended on the other side) stays in the scratch slot
     // ---- initialize_trajectory (transformed_hamiltonian.rs:687-736)
     NM_MARK(C, 0)
@@ -2295,22 +2182,11 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                 const auto mlz = C.edge_z(left_slot), mlv = C.edge_v(left_slot);
                 const auto mrz = C.edge_z(right_slot), mrv = C.edge_v(right_slot);
                 if (depth == 0) {
-#if NM_TRIM_FIRST
                     return turning_regs(E, O, fwd, C.red);        // (initial point, leaf): both in registers
-#else
-#pragma unroll
-                    for (int m = 0; m < DPL / 2; ++m) {
-                        double2 az = fwd ? C.ld2(mlz.r, mlz.so, m) : C.ld2(mrz.r, mrz.so, m);
-                        double2 av = fwd ? C.ld2(mlv.r, mlv.so, m) : C.ld2(mrv.r, mrv.so, m);
-                        turn_acc(az.x, av.x, O.z.a[2 * m], O.v.a[2 * m], s1, s2); turn_acc(az.y, av.y, O.z.a[2 * m + 1], O.v.a[2 * m + 1], s1, s2);
-                    }
-                    C.red.sum2(s1, s2);
-                    return turn_sign(fwd, s1) | turn_sign(fwd, s2);
-#endif
                 } else {
                     // other.first (leaf 0 of this doubling): F[depth]; at depth 1 it is still E
                     const int so_ofz = C.soS(slot_F((int)depth)), so_ofv = C.soS(slot_F((int)depth) + 1);
-                    const bool of_in_regs = NM_TRIM_FIRST && depth == 1;
+                    const bool of_in_regs = depth == 1;
                     // The reference's three pairs (src/nuts.rs:143-161), each written (earlier in the trajectory, later):
                     //   forward   (tree.left, other.right) (tree.right, other.right) (tree.left, other.left)     other.right = O, other.left = its first leaf
                     //   backward  (other.left, tree.right) (other.right, tree.right) (other.left, tree.left)     other.left = O, other.right = its first leaf
@@ -2318,7 +2194,7 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                     // are (left, O) (right, O) (X, first leaf) with X = the tree's edge FAR from `other`: left going forward, right going
                     // backward.  One loop per direction (they differ in one operand; selecting it per element would be 8 v_cndmask per row).
                     auto rows = [&](auto far_is_left, auto of_regs) __attribute__((always_inline)) {
-                        constexpr bool OFR = decltype(of_regs)::value;       // other.first is in registers (E at depth 1, FDz / FDv with NM_FD)
+                        constexpr bool OFR = decltype(of_regs)::value;       // other.first is in registers (E at depth 1, FDz / FDv with FD)
                         auto row = [&](int m, double2 oz, double2 ov) __attribute__((always_inline)) {
                             double2 lz, lv, rz, rv;
                             if constexpr (RE) {
@@ -2339,7 +2215,7 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                             for (int m0 = 0; m0 < DPL / 2; m0 += (TCH > 0 ? TCH : 1)) {
                                 double2 ozb[TCH > 0 ? TCH : 1], ovb[TCH > 0 ? TCH : 1];
 #pragma unroll
-                                for (int c = 0; c < TCH; ++c) if (m0 + c < DPL / 2) { ozb[c] = NM_TLD(C.rs, so_ofz, m0 + c, E.z); ovb[c] = NM_TLD(C.rs, so_ofv, m0 + c, E.v); }
+                                for (int c = 0; c < TCH; ++c) if (m0 + c < DPL / 2) { ozb[c] = C.ld2(C.rs, so_ofz, m0 + c); ovb[c] = C.ld2(C.rs, so_ofv, m0 + c); }
                                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                                 for (int c = 0; c < TCH; ++c) if (m0 + c < DPL / 2) row(m0 + c, ozb[c], ovb[c]);
@@ -2351,7 +2227,7 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                             double2 oz, ov;
                             if constexpr (FD) { oz = make_double2(FDz.a[2 * m], FDz.a[2 * m + 1]); ov = make_double2(FDv.a[2 * m], FDv.a[2 * m + 1]); }   // leaf 0 of this doubling
                             else if constexpr (OFR) { oz = make_double2(E.z.a[2 * m], E.z.a[2 * m + 1]); ov = make_double2(E.v.a[2 * m], E.v.a[2 * m + 1]); }
-                            else { oz = NM_TLD(C.rs, so_ofz, m, E.z); ov = NM_TLD(C.rs, so_ofv, m, E.v); }
+                            else { oz = C.ld2(C.rs, so_ofz, m); ov = C.ld2(C.rs, so_ofv, m); }
                             row(m, oz, ov);
                             NM_GROUP_BARRIER(m);
                         }
@@ -2364,10 +2240,6 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
         };
         if (depth == 0) {
             // a single leaf from the initial point, which E has held since initialize_trajectory: E -> O
-#if !NM_TRIM_FIRST
-            { const int es = fwd ? right_slot : left_slot;
-              C.loadRef(E.z, C.edge_z(es)); C.loadRef(E.v, C.edge_v(es)); C.loadRef(E.g, C.edge_g(es)); }
-#endif
             if constexpr (NOG) leapfrog<DPL, W, Dens, 2, 2>(C, E, O, epsilon, (Tile<DPL>*)nullptr, (Tile<DPL>*)nullptr, C.edge_g(0), gsh);
             else leapfrog<DPL, W, Dens, 2>(C, E, O, epsilon, (Tile<DPL>*)nullptr, (Tile<DPL>*)nullptr);
             O.idx = edge_idx + (int64_t)sign;
@@ -2397,7 +2269,7 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                 NM_MARK(C, 16)
                 if constexpr (NOG) {
                     if (n == 0 && g_from_slot) leapfrog<DPL, W, Dens, 2, 2>(C, O, E, epsilon, (Tile<DPL>*)nullptr, (Tile<DPL>*)nullptr, C.edge_g(0), gsh);
-                    else if (NM_GTILE && !(n == 0 && !reuse_edge)) leapfrog<DPL, W, Dens, 2, 3>(C, O, E, epsilon, (Tile<DPL>*)nullptr, (Tile<DPL>*)nullptr, C.edge_g(0), gsh);
+                    else if (!(n == 0 && !reuse_edge)) leapfrog<DPL, W, Dens, 2, 3>(C, O, E, epsilon, (Tile<DPL>*)nullptr, (Tile<DPL>*)nullptr, C.edge_g(0), gsh);
                     else leapfrog<DPL, W, Dens, 2, 1>(C, O, E, epsilon, (Tile<DPL>*)nullptr, (Tile<DPL>*)nullptr, C.edge_g(0), gsh);
                 } else
                 leapfrog<DPL, W, Dens, 2>(C, O, E, epsilon, (Tile<DPL>*)nullptr, (Tile<DPL>*)nullptr);
@@ -2407,7 +2279,7 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                 if (stop != STOP_NONE) break;
                 // ---- odd leaf n + 1
                 NM_MARK(C, 18)
-                if constexpr (NOG) leapfrog<DPL, W, Dens, 2, (NM_GTILE ? 3 : 1)>(C, E, O, epsilon, (Tile<DPL>*)nullptr, (Tile<DPL>*)nullptr, C.edge_g(0), gsh);
+                if constexpr (NOG) leapfrog<DPL, W, Dens, 2, 3>(C, E, O, epsilon, (Tile<DPL>*)nullptr, (Tile<DPL>*)nullptr, C.edge_g(0), gsh);
                 else
                 leapfrog<DPL, W, Dens, 2>(C, E, O, epsilon, (Tile<DPL>*)nullptr, (Tile<DPL>*)nullptr);
                 NM_MARK(C, 19)
@@ -2432,7 +2304,7 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                         const int so_afz = C.soS(slot_F(fa)), so_afv = C.soS(slot_F(fa) + 1);
                         const int so_alz = C.soS(slot_L(MD, k - 1)), so_alv = C.soS(slot_L(MD, k - 1) + 1);
                         double s1 = 0., s2 = 0., s3 = 0., s4 = 0., s5 = 0., s6 = 0.;
-                        // (NOG: A.first is the doubling's first leaf when the sub-tree starts there — registers FDz / FDv instead of the slot F[depth])
+                        // (FD: A.first is the doubling's first leaf when the sub-tree starts there — registers FDz / FDv instead of the slot F[depth])
                         auto level_rows = [&](auto a_in_fd) __attribute__((always_inline)) {
                         constexpr bool AFD = decltype(a_in_fd)::value;
                         if (k == 2) {
@@ -2458,7 +2330,7 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                                 for (int m0 = 0; m0 < DPL / 2; m0 += (TCH > 0 ? TCH : 1)) {
                                     double2 azb[TCH > 0 ? TCH : 1], avb[TCH > 0 ? TCH : 1];
 #pragma unroll
-                                    for (int c = 0; c < TCH; ++c) if (m0 + c < DPL / 2) { azb[c] = NM_TLD(C.rs, so_afz, m0 + c, E.z); avb[c] = NM_TLD(C.rs, so_afv, m0 + c, E.v); }
+                                    for (int c = 0; c < TCH; ++c) if (m0 + c < DPL / 2) { azb[c] = C.ld2(C.rs, so_afz, m0 + c); avb[c] = C.ld2(C.rs, so_afv, m0 + c); }
                                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                                     for (int c = 0; c < TCH; ++c) if (m0 + c < DPL / 2) row2(m0 + c, azb[c], avb[c]);
@@ -2469,7 +2341,7 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                             for (int m = 0; m < DPL / 2; ++m) {
                                 double2 az, av;
                                 if constexpr (AFD) { az = make_double2(FDz.a[2 * m], FDz.a[2 * m + 1]); av = make_double2(FDv.a[2 * m], FDv.a[2 * m + 1]); }
-                                else { az = NM_TLD(C.rs, so_afz, m, E.z); av = NM_TLD(C.rs, so_afv, m, E.v); }
+                                else { az = C.ld2(C.rs, so_afz, m); av = C.ld2(C.rs, so_afv, m); }
                                 row2(m, az, av);
                                 NM_GROUP_BARRIER(m);
                             }
@@ -2496,9 +2368,9 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                                     double2 azb[T3], avb[T3], lzb[T3], lvb[T3], bzb[T3], bvb[T3];
 #pragma unroll
                                     for (int c = 0; c < TCH3; ++c) if (m0 + c < DPL / 2) {
-                                        azb[c] = NM_TLD(C.rs, so_afz, m0 + c, E.z); avb[c] = NM_TLD(C.rs, so_afv, m0 + c, E.v);
-                                        lzb[c] = NM_TLD(C.rs, so_alz, m0 + c, O.z); lvb[c] = NM_TLD(C.rs, so_alv, m0 + c, O.v);
-                                        bzb[c] = NM_TLD(C.rs, so_bfz, m0 + c, E.v); bvb[c] = NM_TLD(C.rs, so_bfv, m0 + c, O.z);
+                                        azb[c] = C.ld2(C.rs, so_afz, m0 + c); avb[c] = C.ld2(C.rs, so_afv, m0 + c);
+                                        lzb[c] = C.ld2(C.rs, so_alz, m0 + c); lvb[c] = C.ld2(C.rs, so_alv, m0 + c);
+                                        bzb[c] = C.ld2(C.rs, so_bfz, m0 + c); bvb[c] = C.ld2(C.rs, so_bfv, m0 + c);
                                     }
                                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -2510,9 +2382,9 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                             for (int m = 0; m < DPL / 2; ++m) {
                                 double2 az, av;
                                 if constexpr (AFD) { az = make_double2(FDz.a[2 * m], FDz.a[2 * m + 1]); av = make_double2(FDv.a[2 * m], FDv.a[2 * m + 1]); }
-                                else { az = NM_TLD(C.rs, so_afz, m, E.z); av = NM_TLD(C.rs, so_afv, m, E.v); }
-                                const double2 lz = NM_TLD(C.rs, so_alz, m, O.z), lv = NM_TLD(C.rs, so_alv, m, O.v);
-                                const double2 bz2 = NM_TLD(C.rs, so_bfz, m, E.v), bv2 = NM_TLD(C.rs, so_bfv, m, O.z);
+                                else { az = C.ld2(C.rs, so_afz, m); av = C.ld2(C.rs, so_afv, m); }
+                                const double2 lz = C.ld2(C.rs, so_alz, m), lv = C.ld2(C.rs, so_alv, m);
+                                const double2 bz2 = C.ld2(C.rs, so_bfz, m), bv2 = C.ld2(C.rs, so_bfv, m);
                                 row3(m, az, av, lz, lv, bz2, bv2);
                                 NM_GROUP_BARRIER(m);
                             }
@@ -2553,25 +2425,19 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                 // F: the even leaf (still in E) is the first leaf of the sub-trees of level >= 2 that start at n.  Stored here,
                 // after the merges: every call of the merge arithmetic waits for all stores in flight, and nothing reads F
                 // before the next pair.  (At depth 1 leaf 0 is still in E when the top-level tests need it.)
-#ifndef NM_X_NO_SCRATCH_STORES   // (timing experiment only: results are wrong without the stores)
                 if (FD && n == 0) { FDz = E.z; FDv = E.v; }          // the doubling's first leaf stays in registers (any depth >= 1)
                 else
-                if ((n & 3) == 0 && (depth > 1 || !NM_TRIM_FIRST)) {
+                if ((n & 3) == 0 && depth > 1) {
                     const int fs = slot_F(n == 0 ? (int)depth : (int)__builtin_ctzll(n));
                     C.storeS(E.z, fs);
                     C.storeS(E.v, fs + 1);
                 }
-#endif
                 if (n + 2 < nleaf) {
                     // O is the last leaf of the pending level-t sub-tree; its candidate leaves the registers
-#ifndef NM_X_NO_SCRATCH_STORES
                     if (t == 1) { C.store(O.z, C.l1z); C.store(O.v, C.l1v); }
                     else { C.storeS(O.z, slot_L(MD, t)); C.storeS(O.v, slot_L(MD, t) + 1); }
                     if (sub_cand.slot == -2) sub_cand.slot = cand_to_pool(C, used, O.z);
                     else if (sub_cand.slot == -3) sub_cand.slot = cand_to_pool(C, used, E.z);
-#else
-                    if (sub_cand.slot < 0) sub_cand.slot = 0;
-#endif
                     PendEntry e;
                     e.log_size = sub_log_size; e.cand_logp = sub_cand.logp; e.cand_ke = sub_cand.ke;
                     e.cand_idx = sub_cand.idx; e.cand_slot = sub_cand.slot; e.pad = 0;
@@ -2740,16 +2606,13 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                 // F: the even leaf (still in E) is the first leaf of the sub-trees of level >= 2 that start at n.  Stored here,
                 // after the merges: every call of the merge arithmetic waits for all stores in flight, and nothing reads F
                 // before the next pair.  (At depth 1 leaf 0 is still in E when the top-level tests need it.)
-#ifndef NM_X_NO_SCRATCH_STORES   // (timing experiment only: results are wrong without the stores)
-                if ((n & 3) == 0 && (depth > 1 || !NM_TRIM_FIRST)) {
+                if ((n & 3) == 0 && depth > 1) {
                     const int fs = slot_F(n == 0 ? (int)depth : (int)__builtin_ctzll(n));
                     C.storeS(E.z, fs);
                     C.storeS(E.v, fs + 1);
                 }
-#endif
                 if (n + 2 < nleaf) {
                     // O is the last leaf of the pending level-t sub-tree; its candidate leaves the registers
-#ifndef NM_X_NO_SCRATCH_STORES
                     if (t == 1) { C.store(O.z, C.l1z); C.store(O.v, C.l1v); }
                     else { C.storeS(O.z, slot_L(MD, t)); C.storeS(O.v, slot_L(MD, t) + 1); }
                     if (!BATCH || chunk_end) {
@@ -2757,9 +2620,6 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                     else if (sub_cand.slot == -3) sub_cand.slot = cand_to_pool(C, used, E.z);
                     else if (sub_cand.slot >= NM_RING) sub_cand.slot = ring_to_pool(C, used, sub_cand.slot - NM_RING);
                     }
-#else
-                    if (sub_cand.slot < 0) sub_cand.slot = 0;
-#endif
                     if (!BATCH || chunk_end) {       // (batched: only a whole chunk becomes a pending sub-tree, of level t >= 6)
                     PendEntry e;
                     e.log_size = sub_log_size; e.cand_logp = sub_cand.logp; e.cand_ke = sub_cand.ke;
@@ -2809,9 +2669,6 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
             } else {
             C.storeRef(O.z, C.edge_z(ns)); C.storeRef(O.v, C.edge_v(ns)); if constexpr (!NOG) C.storeRef(O.g, C.edge_g(ns));
             }
-#ifdef NM_EXTRA_TRAFFIC   // development: is the kernel bound by the bytes it moves? (two more tile stores per doubling)
-            C.storeS(O.v, slot_F(MD)); C.storeS(O.z, slot_F(MD) + 1);
-#endif
             if (fwd) right_slot = ns; else left_slot = ns;
             o_is_edge = true; o_edge_sign = sign;
         }
@@ -2820,9 +2677,6 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
         if constexpr (kin_trait<Dens>::value) { if (fwd) right_ke = O.ke; else left_ke = O.ke; }
         depth += 1;
         log_size = total;
-#ifdef NM_X_SABOTAGE_LR41   // (tools/runs/gpu_r06p.sh only: ONE deliberately wrong instantiation, to show that the known-answer checks reject it)
-        if constexpr (DPL == 4 && W == 1 && lr_trait<Dens>::value) log_size = 0.5 * total;
-#endif
         if (turning && !in_extra) { in_extra = true; extra_left = s.extra_doublings; }
     }
     R.depth = depth;
@@ -2840,15 +2694,16 @@ template <int DPL, int W, class Dens>
 NM_DEV void write_row(ChainCtx<DPL, W, Dens>& C, double* base, size_t row, const Tile<DPL>& t, bool positions = false) {
     if (!base) return;
     double* dst = base + row + C.goff;
-#if NM_WRITE_ROW_BUF
-  if (NM_WRITE_ROW_BUF == 1 || positions) {
-    // One buffer descriptor per row (its base is wave-uniform), a lane's pair of elements (2 t, 2 t + 1) as ONE 16-byte store, the
-    // rows beyond dim cut off by the descriptor's range (whole pairs: the range ends on a pair boundary, an odd last element is
-    // written by its lane below): DPL / 2 coalesced stores instead of DPL masked 8-byte stores with a 64-bit address each.
+  if (positions) {
+    // The position row — the one output every caller takes — through one buffer descriptor per row (its base is wave-uniform), a lane's pair
+    // of elements (2 t, 2 t + 1) as ONE non-temporal 16-byte store, the rows beyond dim cut off by the descriptor's range (whole pairs: the
+    // range ends on a pair boundary, an odd last element is written by its lane below): DPL / 2 coalesced stores instead of DPL masked 8-byte
+    // stores with a 64-bit address each.  The other vector outputs keep the masked stores: the kernel is at its register cap and the form that
+    // touches the least code won (K2, 200 recorded draws: 75.8 ms all masked, 73.4 all buffered, 72.1 this; profiles/r04zz_write_row_variants.txt).
     const int whole = C.dim & ~1;
     const rsrc_t r = make_rsrc(dst, (uint64_t)whole * 8);
 #pragma unroll
-    for (int m = 0; m < DPL / 2; ++m) buf_store2_aux<NM_ROW_AUX>(r, C.voff + m * (64 * W * 16), 0, t.a[2 * m], t.a[2 * m + 1]);
+    for (int m = 0; m < DPL / 2; ++m) buf_store2_aux<2>(r, C.voff + m * (64 * W * 16), 0, t.a[2 * m], t.a[2 * m + 1]);
     if (C.dim & 1) {
 #pragma unroll
         for (int m = 0; m < DPL / 2; ++m)
@@ -2856,7 +2711,6 @@ NM_DEV void write_row(ChainCtx<DPL, W, Dens>& C, double* base, size_t row, const
     }
     return;
   }
-#endif
 #pragma unroll
     for (int k = 0; k < DPL; ++k) {
         int d = C.elem(k);
@@ -3384,20 +3238,10 @@ NM_DEV void lr_resume(ChainCtx<DPL, W, Dens>& C, uint64_t chain) {
 // ---------------------------------------------------------------------------------------------
 // Minimum waves per SIMD the register allocator must leave room for (second __launch_bounds__ argument): the small
 // tilings are latency-bound with few lanes busy, so more resident chains per CU beat a spill-free allocation there.
-#ifndef NM_OCC_DPL2
-#define NM_OCC_DPL2 2    // <= 256 VGPRs.  (Rounds 1-2: 4 waves / 128 VGPRs, K4 +17 %, K3 +6 %.  Round 3, with the batched merges: at 128 the
-                         // leaf loop spills (205 VGPRs) and one funnel chain needs 2.15 us per leapfrog; at 256 nothing spills: 1.56 us, and
-                         // 8192 chains run at 9.7e8 leapfrogs/s against 6.7e8 — profiles/r03g_*)
-#endif
-#ifndef NM_OCC_DPL4
-#define NM_OCC_DPL4 2    // the DPL 4 kernels sit at 252..262 VGPRs: pin them below 256 (neutral for the elementwise densities,
-#endif                  // x1.6 for the full-precision normal, whose GEMV needs the second wave to hide L2 latency)
-#ifndef NM_OCC_DPL8_W2
-#define NM_OCC_DPL8_W2 2   // (8 doubles, 2 waves): 1.62e11 on K2 against 1.81e11 for (16, 1) — used only on request
-#endif
-#ifndef NM_OCC_DPL8
-#define NM_OCC_DPL8 2    // <= 256 VGPRs (72 spilled): dims 257..512 +18 % (two chains per SIMD hide each other's latency)
-#endif
+constexpr int NM_OCC_DPL2 = 2;      // <= 256 VGPRs: at 4 waves / 128 VGPRs the leaf loop of the batched merges spills, 6.7e8 against 9.7e8 leapfrogs/s (profiles/r03g_*)
+constexpr int NM_OCC_DPL4 = 2;      // the DPL 4 kernels sit at 252..262 VGPRs: pinned below 256 (neutral for the elementwise densities, x1.6 for the full-precision normal)
+constexpr int NM_OCC_DPL8_W2 = 2;   // (8 doubles, 2 waves): 1.62e11 on K2 against 1.81e11 for (16, 1) — used only on request
+constexpr int NM_OCC_DPL8 = 2;      // <= 256 VGPRs (72 spilled): dims 257..512 +18 % (two chains per SIMD hide each other's latency)
 template <int DPL, int W>
 constexpr int draw_min_waves() {
     if (W == 2 && DPL == 8) return NM_OCC_DPL8_W2;

@@ -315,9 +315,6 @@ struct LPend {
 
 // Development (-DNM_LANE_PROF=1, tools/prof_lane.py): the wave-level timeline of block 0.  A mark charges the shader-clock cycles
 // since the wave's previous mark (kept in LDS: ONE clock per wave, so serialised divergent paths are charged once each) to `slot`.
-#ifndef NM_LANE_STORE_GUARD
-#define NM_LANE_STORE_GUARD 1
-#endif
 #ifndef NM_LANE_PROF
 #define NM_LANE_PROF 0
 #endif
@@ -364,9 +361,7 @@ struct LCtx {
     NM_DEV static void bst(rsrc_t r, int off, double a) {
         v2u q; q.x = (unsigned)__double2loint(a); q.y = (unsigned)__double2hiint(a);
         __builtin_amdgcn_raw_buffer_store_b64(q, r, off, 0, 0);
-#if NM_LANE_STORE_GUARD
-        asm volatile("s_nop 1" ::"v"(q));
-#endif
+        asm volatile("s_nop 1" ::"v"(q));     // the store-data hazard (nuts_kernels.hpp buf_store2)
     }
     NM_DEV double ldWe(int slot, int e) const { return bld(rw, l8 + (slot * E + e) * 512); }
     NM_DEV void stWe(int slot, int e, double a) const { bst(rw, l8 + (slot * E + e) * 512, a); }
@@ -1342,13 +1337,11 @@ NM_DEV void l_chain_draw(LCtx<NP, LD>& C, uint64_t chain, uint64_t t_out) {
 // tree depths differ most, two thirds of the leapfrog slots are idle (23 slots per draw for a mean of 7.7 leaves per lane).
 // Here a lane's transition is a STATE MACHINE around ONE leapfrog site: every round each lane that is inside a tree takes one leapfrog
 // of ITS tree (whatever doubling, direction or leaf it is at) and advances its own bookkeeping.  Draws begin and end at EPOCH boundaries
-// (every NM_LANE_EPOCH rounds): the begin / end phases — momentum refresh, the chosen point's recomputation, adaptation, the statistics
+// (an epoch was 4 rounds, set by the launch form nuts_lane_rounds_kernel, which round 5 removed: see the note above LaneShared; nothing
+// sets an epoch length now, the step functions here are unreferenced templates): the begin / end phases — momentum refresh, the chosen point's recomputation, adaptation, the statistics
 // row: as long as several leaves — run once per epoch for all lanes that are ready instead of once per round for whoever is ready.
 // Same arithmetic per chain, same generator stream per chain: the same bits as every other kernel.
 // =================================================================================================================
-#ifndef NM_LANE_EPOCH
-#define NM_LANE_EPOCH 4
-#endif
 enum LanePhase : int { LP_BEGIN = 0, LP_LEAF = 1, LP_END = 2, LP_DONE = 3 };
 
 template <int NP>
