@@ -1653,8 +1653,24 @@ NM_DEV bool mass_matrix_adapt(ChainCtx<DPL, W, Dens>& C, const Tile<DPL>& dm, co
     return true;
 }
 
+// The sampling-phase build of the wave-per-chain draw kernel (template parameter SAMPLING of nuts_draw_kernel, chain_draw and adapt; KernelKind
+// K_DRAW_SAMPLING).  Every draw of such a launch has an index > num_tune on every chain (the host proves it: nuts_engine.hip, sampling_from),
+// so the transformation and the dual-averaging / Adam state are frozen: `adapt` is its `draw >= num_tune` arm alone — the estimators, the
+// mass-matrix update and the step-size search are not instantiated — and the stores of x / g_x that only the warm-up reads are gone.  The
+// general build (SAMPLING = false) is the code as it was.  For the one-wavefront tilings of 8 and 16 doubles per lane of the plain built-in
+// densities.  Two things such a launch never executes stay in the build, both measured (profiles/r07_k2_sampling_kernel_ab.txt):
+//   the lazy re-whitening arm of nuts_transition: without it the register allocation of the (16, 1) pair loop comes out worse (K2 2.58e11
+//   against 2.64e11 with it, 2.59e11 for the general kernel);
+//   the two uexp of a frozen log step per draw (the step size, the row's step_size_bar): taken once per chain per launch, in a register or
+//   in LDS, the value costs that kernel 13 to 35 more spilled SGPRs and up to 16 B of scratch.
+template <class Dens> constexpr bool sampling_density() {
+    return std::is_same<Dens, IidNormal>::value || std::is_same<Dens, DiagNormal>::value || std::is_same<Dens, Funnel>::value ||
+           std::is_same<Dens, MvnPrec>::value;          // (the 8 schools run on the 2-doubles tiling alone)
+}
+template <int DPL, int W, class Dens> constexpr bool has_sampling_build() { return plain_unit && W == 1 && (DPL == 8 || DPL == 16) && sampling_density<Dens>(); }
+
 // GlobalStrategy::adapt (reference src/adapt_strategy.rs:121-222).  x, gx = chosen draw.
-template <int DPL, int W, class Dens>
+template <int DPL, int W, class Dens, bool SAMPLING = false>
 NM_DEV uint64_t adapt(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col, bool is_good,
                       const Tile<DPL>& x, const Tile<DPL>& gx) {
     const nm_settings& s = C.P.s;
@@ -1664,6 +1680,11 @@ NM_DEV uint64_t adapt(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col, bool is_g
     sc.last_sym_mean_tree_accept = col.mean_sym();
     sc.last_n_steps = col.count;
     sc.last_max_energy_error = col.max_energy_error;
+    if constexpr (SAMPLING) {                                    // the arm below, and nothing else of this function
+        update_stepsize(C, true);
+        sc.tuning = 0;
+        return NM_CHAIN_OK;
+    }
     if (draw >= s.num_tune) {
         update_stepsize(C, true);
         sc.tuning = 0;
@@ -3016,7 +3037,7 @@ NM_DEV bool chain_draw_mclmc(ChainCtx<DPL, W, Dens>& C, uint64_t chain, uint64_t
     return sc.status == NM_CHAIN_OK;
 }
 
-template <int DPL, int W, class Dens>
+template <int DPL, int W, class Dens, bool SAMPLING = false>
 NM_DEV void chain_draw(ChainCtx<DPL, W, Dens>& C, uint64_t chain, uint64_t t_out) {
     const KParams& P = C.P;
     ChainScalars& sc = C.sc;
@@ -3062,7 +3083,7 @@ NM_DEV void chain_draw(ChainCtx<DPL, W, Dens>& C, uint64_t chain, uint64_t t_out
         // x and g_x of the current point are consumed from memory only by the warm-up (re-whitening, step-size
         // search), by the divergence statistics and by the host after the launch; in between they are skipped
         // (sc.px_stale) and, should a later draw stay on its initial point, rebuilt from P_Z exactly as here.
-        const bool need_x = sc.tuning || t_out + 1 == P.n_draws || P.out_div_start || P.out_div_start_grad;
+        const bool need_x = (!SAMPLING && sc.tuning) || t_out + 1 == P.n_draws || P.out_div_start || P.out_div_start_grad;
         if (need_x) { C.storeP_nt(x, P_X); C.storeP_nt(gx, P_GX); }
         sc.px_stale = need_x ? 0 : 1;
         C.storeP(z, P_Z); C.storeP(gz, P_GZ);
@@ -3083,7 +3104,7 @@ NM_DEV void chain_draw(ChainCtx<DPL, W, Dens>& C, uint64_t chain, uint64_t t_out
     const int64_t trans_id = sc.transform_id;
     sc.total_steps += col.count;
     NM_MARK(C, 3)
-    uint64_t ast = adapt(C, col, is_good, x, gx);
+    uint64_t ast = adapt<DPL, W, Dens, SAMPLING>(C, col, is_good, x, gx);
     NM_MARK(C, 4)
     if (ast != NM_CHAIN_OK) sc.status = ast;
     out.depth = R.depth; out.maxdepth_reached = R.reached_maxdepth; out.diverging = R.diverging;
@@ -3268,8 +3289,9 @@ NM_DEV ClusterLink cluster_start(const KParams& P, double* red_lds, unsigned cl_
 }
 #endif
 
-template <int DPL, int W, class Dens>
+template <int DPL, int W, class Dens, bool SAMPLING = false>
 __global__ __launch_bounds__(64 * W, (draw_min_waves<DPL, W>())) __attribute__((amdgpu_flat_work_group_size(64 * W, 64 * W))) void nuts_draw_kernel(const KParams P) {
+    static_assert(!SAMPLING || has_sampling_build<DPL, W, Dens>(), "the sampling-phase build exists for the plain one-wavefront tilings of 8 / 16 doubles per lane");
     __shared__ BlockShared<DPL, W, Dens> sh;
     dm_init_lds();
 #if NM_CLUSTER_MODE
@@ -3323,7 +3345,7 @@ __global__ __launch_bounds__(64 * W, (draw_min_waves<DPL, W>())) __attribute__((
                     while (C.sc.draw_count < P.draw_end) { if (!chain_draw_lr(C, chain)) break; }
             } else {
             for (uint64_t t = 0; t < P.n_draws; ++t) {
-                chain_draw(C, chain, t);
+                chain_draw<DPL, W, Dens, SAMPLING>(C, chain, t);
                 if (C.sc.status != NM_CHAIN_OK) break;
             }
             }

@@ -17,7 +17,9 @@
 namespace nm {
 enum KernelKind { K_INIT, K_DRAW, K_QUERY,      // K_QUERY: resident blocks per CU of the draw kernel
                   K_GROUP_DRAW, K_GROUP_TUNE, K_GROUP_QUERY,    // the small-chain kernels of nuts_group.hpp (dim <= 64): sampling / warm-up
-                  K_GROUP_DRAW_ROOMY, K_GROUP_TUNE_ROOMY };     // ... compiled for one wavefront per SIMD (grids of at most 4 x CUs blocks; built-in densities)
+                  K_GROUP_DRAW_ROOMY, K_GROUP_TUNE_ROOMY,       // ... compiled for one wavefront per SIMD (grids of at most 4 x CUs blocks; built-in densities)
+                  K_DRAW_SAMPLING };    // the draw kernel's sampling-phase build (nuts_kernels.hpp has_sampling_build): launches whose draws all have an index > num_tune.
+                                        // (Last, so that the kinds a density module was built with keep their values; a module is never asked for this one.)
 
 // the small-chain kernels exist for the densities that have a group form (nuts_group.hpp); the group size follows P.dim
 #define NM_LAUNCH_GROUP_NS(NS)                                                                                            \
@@ -58,8 +60,24 @@ inline hipError_t launch_t(KernelKind kind, const KParams& P, unsigned grid_bloc
 #else
     if (is_group_kind(kind)) return hipErrorInvalidValue;      // (the small-chain kernels live in part 1)
 #endif
-    if (kind == K_QUERY) return hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, nuts_draw_kernel<DPL, W, Dens>, 64 * W, 0);
+    if (kind == K_QUERY) {
+        hipError_t st = hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, nuts_draw_kernel<DPL, W, Dens>, 64 * W, 0);
+        if constexpr (has_sampling_build<DPL, W, Dens>()) {      // one grid serves both builds (the tree scratch belongs to the block): the tighter answer
+            int b = 0;
+            if (st == hipSuccess) st = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, nuts_draw_kernel<DPL, W, Dens, true>, 64 * W, 0);
+            if (st == hipSuccess && b < *occ) *occ = b;
+        }
+        return st;
+    }
     dim3 grid(grid_blocks), block(64 * W);
+    if (kind == K_DRAW_SAMPLING) {                               // a missing build is an error, never the general kernel in its place
+        if constexpr (has_sampling_build<DPL, W, Dens>()) {
+            hipLaunchKernelGGL((nuts_draw_kernel<DPL, W, Dens, true>), grid, block, 0, stream, P);
+            return hipGetLastError();
+        } else {
+            return hipErrorInvalidValue;
+        }
+    }
     if (kind == K_INIT) hipLaunchKernelGGL((nuts_init_kernel<DPL, W, Dens>), grid, block, 0, stream, P);
     else hipLaunchKernelGGL((nuts_draw_kernel<DPL, W, Dens>), grid, block, 0, stream, P);
     return hipGetLastError();
