@@ -13,7 +13,7 @@ chains' `is_good` draws count, like the reference's collector), the ranks exchan
 ONE all_gather per window (torch.distributed: RCCL over xGMI with the nccl backend, issued on a side stream so the next
 window's kernel is already running; gloo in the tests), merge them in rank order with Chan's formula, and every rank
 sets sigma = (var_x / var_g)^(1/4), mean = x_bar + sigma^2 g_bar (the reference's diagonal estimate,
-src/transform/diagonal.rs:107-131) for all its chains with one broadcast upload (nm_engine_set_transform).
+src/transform/diagonal.rs:107-131) for all its chains with one upload and one scatter kernel (nm_engine_set_transform).
 `pooled_welford` is the merge with numpy arrays (pinned by tests/test_distributed_cpu.py).
 """
 import numpy as np

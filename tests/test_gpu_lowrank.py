@@ -542,3 +542,72 @@ def test_k5_full_size_properties(oracle):
                                         x0[:2], draws, n_threads=2, transform=tr)
     assert failed == 0
     assert_bit_exact(pos[:, :2], st[:, :2], pos_o, st_o)
+
+
+# ---- nm_engine_set_transform: refusals, rank 0, and what reaches the device ------------------------------------------------
+def fixed_diag_run(oracle, dim, transform):
+    """3 chains x 30 draws of a diagonal normal under a frozen transformation, engine and oracle"""
+    rng = np.random.default_rng(1000 + dim)
+    logp = N.LogpSpec.diag_normal(np.exp(rng.uniform(-2, 2, dim)))
+    s = lowrank_settings(num_chains=3, seed=43, num_tune=20, freeze_transform=True)
+    return run_fixed(oracle, logp, s, 3, transform, 30)
+
+
+@pytest.mark.parametrize("poison", ["nan_std", "inf_val", "nan_vec"])
+@pytest.mark.parametrize("dim,rank", [(5, 2), (70, 3)])
+def test_set_transform_refuses_one_chain(oracle, dim, rank, poison):
+    """LowRankMassMatrix::update returns early on non-finite input: chain 1 keeps the transformation it had (its slots on the
+    device are not written), chains 0 and 2 take theirs.  Both dims run on the (2 doubles, 1 wave) tiling: 123 / 58 padding elements."""
+    stds, mean, vals, vecs, mu = random_transform(np.random.default_rng(7 * dim + rank), dim, rank, per_chain=3)
+    if poison == "nan_std":
+        stds[1, 0] = np.nan
+    elif poison == "inf_val":
+        vals[1, 0] = np.inf
+    else:
+        vecs[1, 0, 0] = np.nan
+    pos, st, pos_o, st_o = fixed_diag_run(oracle, dim, (stds, mean, vals, vecs, mu))
+    assert_bit_exact(pos, st, pos_o, st_o)
+    assert st["transformation_update_id"][0].tolist() == [1, 0, 1]
+    assert st["num_eigenvalues"][0].tolist() == [rank, 0, rank]
+
+
+def test_set_transform_refuses_shared(oracle):
+    stds, mean, vals, vecs, mu = random_transform(np.random.default_rng(19), 5, 2)
+    stds[0] = np.nan
+    pos, st, pos_o, st_o = fixed_diag_run(oracle, 5, (stds, mean, vals, vecs, mu))
+    assert_bit_exact(pos, st, pos_o, st_o)
+    assert (st["transformation_update_id"][0] == 0).all()
+
+
+@pytest.mark.parametrize("dim", [5, 70])
+def test_set_transform_rank_zero_per_chain(oracle, dim):
+    stds, mean, _, _, mu = random_transform(np.random.default_rng(23 + dim), dim, 1, per_chain=3)
+    pos, st, pos_o, st_o = fixed_diag_run(oracle, dim, (stds, mean, np.zeros((3, 0)), np.zeros((3, 0, dim)), mu))
+    assert_bit_exact(pos, st, pos_o, st_o)
+    assert (st["num_eigenvalues"][0] == 0).all() and (st["transformation_update_id"][0] == 1).all()
+
+
+def test_set_transform_round_trip_through_lowrank():
+    """What ChainBatch.lowrank() reads back after set_transform is what went in, per chain and then shared at a smaller rank
+    (slots at or beyond n_eig may keep what they held: nothing is asserted about them)."""
+    dim, n = 70, 3
+    rng = np.random.default_rng(29)
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint64)
+    s = lowrank_settings(num_chains=n, seed=5, num_tune=20, freeze_transform=True)
+    b = N.ChainBatch(s, N.LogpSpec.diag_normal(np.exp(rng.uniform(-2, 2, dim))), n)
+    assert (b.set_position(b.init_positions_uniform()) == 0).all()
+    stds, mean, vals, vecs, mu = random_transform(rng, dim, 3, per_chain=n)
+    b.set_transform(stds, mean, vals, vecs, mu)
+    b.draw_many(1)
+    n_eig, got_vals, got_vecs, got_mu = b.lowrank()
+    assert (n_eig == 3).all()
+    assert (bits(got_vals[:, :3]) == bits(np.sqrt(vals))).all()
+    assert (bits(got_vecs[:, :3, :]) == bits(vecs)).all() and (bits(got_mu) == bits(mu)).all()
+    stds, mean, vals, vecs, mu = random_transform(rng, dim, 1)
+    b.set_transform(stds, mean, vals, vecs, mu)
+    b.draw_many(1)
+    n_eig, got_vals, got_vecs, got_mu = b.lowrank()
+    b.close()
+    assert (n_eig == 1).all()
+    assert (bits(got_vecs[:, 0, :]) == bits(vecs[0])[None, :]).all()
+    assert (bits(got_vals[:, 0]) == bits(np.sqrt(vals))[0]).all()
