@@ -685,6 +685,34 @@ NM_HD MergeOut merge_math_impl(double a, double b, uint32_t is_main, uint32_t w_
     return o;
 }
 static __device__ NM_DM_CALL MergeOut merge_math(double a, double b, uint32_t is_main, uint32_t w_lo, uint32_t w_hi) { return merge_math_impl(a, b, is_main, w_lo, w_hi); }
+// The merge INTO THE MAIN TREE (is_main: self_log_size = a) with one exp instead of two (round 8; the sampling build's top-level merge).
+// There p = exp(b - a).  For diff = a - b > 0 that is exp(-diff), the `e` of the logaddexp: b - a and -(a - b) are the same double
+// (x - y = -(y - x) in IEEE arithmetic, and a difference > 0 is no zero).  For diff <= 0, `ge` (b >= a) decides take / draws / fatal
+// whatever p is; for a NaN difference e is the same NaN p was.  Same total, same flags on every pair of doubles
+// (tests/test_merge_math_main.py compares the two on the host).
+NM_HD MergeOut merge_math_main_impl(double a, double b, uint32_t w_lo, uint32_t w_hi) {
+    const double diff = a - b;
+    const double e = exp_sl(diff > 0. ? -diff : diff);
+    const double lp = log1p_unit(e);
+    double total = (diff > 0. ? a : b) + lp;
+    total = (diff > 0. || diff < 0.) ? total : diff;
+    total = a == b ? a + 0x1.62e42fefa39efp-1 : total;
+    const bool ge = b >= a;
+    const double p_ = e;
+    const bool in01 = p_ >= 0.0 && p_ < 1.0;
+    const double ph = __builtin_floor(p_ * 4294967296.0);
+    const double pl = __builtin_floor(__builtin_fma(p_, 18446744073709551616.0, -ph * 4294967296.0));
+    const uint64_t p_int = in01 ? (((uint64_t)(uint32_t)ph << 32) | (uint64_t)(uint32_t)pl) : 0ull;
+    const uint64_t w = ((uint64_t)w_hi << 32) | w_lo;
+    const bool draws = !ge && in01;
+    const bool take = ge || (in01 ? w < p_int : p_ == 1.0);
+    const bool fatal = !ge && !in01 && !(p_ == 1.0);
+    MergeOut o;
+    o.total = total;
+    o.flags = (take && !fatal ? 1u : 0u) | (draws ? 2u : 0u) | (fatal ? 4u : 0u);
+    return o;
+}
+static __host__ __device__ NM_DM_CALL MergeOut merge_math_main(double a, double b, uint32_t w_lo, uint32_t w_hi) { return merge_math_main_impl(a, b, w_lo, w_hi); }
 
 // exp(x) - 1 for the isokinetic momentum refresh (reference f64::exp_m1, transformed_hamiltonian.rs:800-801): the same
 // operation sequence as oracle/nmo_math.hpp det_expm1 (Taylor series to x^14 for |x| <= 0.35, else exp(x) - 1)

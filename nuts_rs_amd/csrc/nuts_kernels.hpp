@@ -1873,13 +1873,22 @@ struct CandRef { int slot; double logp, ke; int64_t idx; };   // slot: -3 live i
 enum TreeStop { STOP_NONE = 0, STOP_TURNING = 1, STOP_DIVERGING = 2, STOP_FATAL = 3 };
 
 // multinomial merge weights (reference merge_into, src/nuts.rs:172-207).  Returns take_B.
-template <int DPL, int W, class Dens>
+// MAIN1: the merge into the main tree with one exp (dev_math.hpp merge_math_main; is_main must be true) — the sampling build's top-level site.
+template <int DPL, int W, class Dens, bool MAIN1 = false>
 NM_DEV bool merge_weights(ChainCtx<DPL, W, Dens>& C, double a_log_size, double b_log_size, bool is_main, double& total, bool& fatal) {
     NM_MARK(C, 13)
     // the whole of merge_into's arithmetic in one branch-free routine (dev_math.hpp merge_math).  The chain's next u64 is read here and
     // consumed only if the routine says random_bool drew it; refilling the word cache early changes nothing (it is a window onto the stream).
     if (!C.rng.has(2)) C.rng.refill();
     const uint32_t off_ = (uint32_t)(C.rng.pos - C.rng.base);
+    if constexpr (MAIN1) {
+        const MergeOut mm = merge_math_main(a_log_size, b_log_size, C.rng.cache[off_], C.rng.cache[off_ + 1]);
+        total = uniform_f64(mm.total);
+        const uint32_t mmf = (uint32_t)__builtin_amdgcn_readfirstlane((int)mm.flags);
+        C.rng.pos += (uint64_t)(mmf & 2u);
+        if (mmf & 4u) fatal = true;
+        return (mmf & 1u) != 0;
+    }
     const MergeOut mo = merge_math(a_log_size, b_log_size, is_main ? 1u : 0u, C.rng.cache[off_], C.rng.cache[off_ + 1]);
     total = uniform_f64(mo.total);
     const uint32_t mf = (uint32_t)__builtin_amdgcn_readfirstlane((int)mo.flags);
@@ -2051,7 +2060,8 @@ NM_DEV int ring_to_pool(ChainCtx<DPL, W, Dens>& C, uint32_t& used, int ring_lane
 
 // nuts::draw (reference src/nuts.rs:281-388).  On entry the chain's current point is in its slots P_*.
 // On exit, if R.chosen.slot >= 0, zc holds the chosen point's z.
-template <int DPL, int W, class Dens>
+// SAMPLING (the sampling-phase build, see `adapt`): the merge into the main tree with one exp (round 8, dev_math.hpp merge_math_main).
+template <int DPL, int W, class Dens, bool SAMPLING = false>
 NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col, DrawResult& R, Tile<DPL>& zc) {
     const nm_settings& s = C.P.s;
     ChainScalars& sc = C.sc;
@@ -2666,7 +2676,7 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
         if (check) turning = top_level_turning();
         NM_MARK(C, 26)
         double total;
-        const bool take = merge_weights(C, log_size, sub_log_size, true, total, fatal);
+        const bool take = merge_weights<DPL, W, Dens, SAMPLING>(C, log_size, sub_log_size, true, total, fatal);
         if (fatal) break;
         if (take) {
             if (mc.slot >= 0) used &= ~(1u << mc.slot);
@@ -3047,7 +3057,7 @@ NM_DEV void chain_draw(ChainCtx<DPL, W, Dens>& C, uint64_t chain, uint64_t t_out
     AcceptCollector col;
     DrawResult R;
     Tile<DPL> x, gx, z, gz;
-    uint64_t st = nuts_transition(C, col, R, z);
+    uint64_t st = nuts_transition<DPL, W, Dens, SAMPLING>(C, col, R, z);
     NM_MARK(C, 2)
     nm_draw_stats out;
     out.draw = sc.draw_count; out.chain = P.chain_id_offset + chain;
