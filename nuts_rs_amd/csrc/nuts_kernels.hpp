@@ -2075,6 +2075,11 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
     // takes the unbatched path differently (profiles/r07_switch_retirement_asm_identity.txt).  Removing it is a change of generated code.
     constexpr bool FD = false;
     constexpr int TCH = (DPL == 16 && W == 1) ? NM_TEST_CHUNK : 0;     // iterations a U-turn test requests its slots' rows ahead (16-doubles tiling)
+    // ROLL (round 9, the sampling-phase build): inside a U-turn test the rows of the scratch slots roll through the landing registers — the first
+    // TCH rows are requested, then row m is computed and row m + TCH requested into the registers it has just freed, one sched_barrier per row
+    // pinning that order — instead of draining between chunks of TCH rows (profiles/r09_k2_test_row_pipeline_ab.txt).  The landing arrays keep
+    // their size; the general build keeps the chunked loops (its generated code still moved a little with this arm: section 3 of that file).
+    constexpr bool ROLL = SAMPLING && TCH > 0;
     [[maybe_unused]] Tile<DPL> Gsh;                        // NOG: g_z of the point the last leapfrog produced (leapfrog's GMODE 3)
     [[maybe_unused]] Tile<DPL>* const gsh = &Gsh;
     [[maybe_unused]] Tile<DPL> FDz, FDv;
@@ -2241,7 +2246,18 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                             if constexpr (decltype(far_is_left)::value) { turn_acc(lz.x, lv.x, oz.x, ov.x, s5, s6); turn_acc(lz.y, lv.y, oz.y, ov.y, s5, s6); }
                             else { turn_acc(rz.x, rv.x, oz.x, ov.x, s5, s6); turn_acc(rz.y, rv.y, oz.y, ov.y, s5, s6); }
                         };
-                        if constexpr (!OFR && TCH > 0) {                     // the slot's rows requested TCH iterations ahead (see the level-k tests)
+                        if constexpr (!OFR && ROLL) {
+                            double2 ozb[TCH > 0 ? TCH : 1], ovb[TCH > 0 ? TCH : 1];
+#pragma unroll
+                            for (int c = 0; c < TCH; ++c) { ozb[c] = C.ld2(C.rs, so_ofz, c); ovb[c] = C.ld2(C.rs, so_ofv, c); }
+                            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                            for (int m = 0; m < DPL / 2; ++m) {
+                                row(m, ozb[m % TCH], ovb[m % TCH]);
+                                if (m + TCH < DPL / 2) { ozb[m % TCH] = C.ld2(C.rs, so_ofz, m + TCH); ovb[m % TCH] = C.ld2(C.rs, so_ofv, m + TCH); }
+                                __builtin_amdgcn_sched_barrier(0);
+                            }
+                        } else if constexpr (!OFR && TCH > 0) {              // the slot's rows requested TCH iterations ahead (see the level-k tests)
 #pragma unroll
                             for (int m0 = 0; m0 < DPL / 2; m0 += (TCH > 0 ? TCH : 1)) {
                                 double2 ozb[TCH > 0 ? TCH : 1], ovb[TCH > 0 ? TCH : 1];
@@ -2354,7 +2370,18 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                                     turn_acc(azj, avj, bz, bv, s5, s6);
                                 }
                             };
-                            if constexpr (!AFD && TCH > 0) {
+                            if constexpr (!AFD && ROLL) {
+                                double2 azb[TCH > 0 ? TCH : 1], avb[TCH > 0 ? TCH : 1];
+#pragma unroll
+                                for (int c = 0; c < TCH; ++c) { azb[c] = C.ld2(C.rs, so_afz, c); avb[c] = C.ld2(C.rs, so_afv, c); }
+                                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                                for (int m = 0; m < DPL / 2; ++m) {
+                                    row2(m, azb[m % TCH], avb[m % TCH]);
+                                    if (m + TCH < DPL / 2) { azb[m % TCH] = C.ld2(C.rs, so_afz, m + TCH); avb[m % TCH] = C.ld2(C.rs, so_afv, m + TCH); }
+                                    __builtin_amdgcn_sched_barrier(0);
+                                }
+                            } else if constexpr (!AFD && TCH > 0) {
                                 // (round 6) the slot's rows REQUESTED TCH iterations ahead of their use: left to itself the compiler issues two loads, waits for
                                 // both, computes, and issues the next two — eight serialised round trips per test at 16 doubles per lane
 #pragma unroll
@@ -2392,7 +2419,24 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                                 }
                             };
                             constexpr int TCH3 = TCH >= 2 ? (TCH / 2 < NM_TEST_CHUNK3_MAX ? TCH / 2 : NM_TEST_CHUNK3_MAX) : 0;      // six loads per iteration here: fewer iterations ahead
-                            if constexpr (!AFD && TCH3 > 0) {
+                            if constexpr (!AFD && ROLL && TCH3 > 0) {         // two rows ahead with the six arrays
+                                constexpr int T3 = TCH3 > 0 ? TCH3 : 1;
+                                double2 azb[T3], avb[T3], lzb[T3], lvb[T3], bzb[T3], bvb[T3];
+                                auto req3 = [&](int c, int m) __attribute__((always_inline)) {
+                                    azb[c] = C.ld2(C.rs, so_afz, m); avb[c] = C.ld2(C.rs, so_afv, m);
+                                    lzb[c] = C.ld2(C.rs, so_alz, m); lvb[c] = C.ld2(C.rs, so_alv, m);
+                                    bzb[c] = C.ld2(C.rs, so_bfz, m); bvb[c] = C.ld2(C.rs, so_bfv, m);
+                                };
+#pragma unroll
+                                for (int c = 0; c < T3; ++c) req3(c, c);
+                                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                                for (int m = 0; m < DPL / 2; ++m) {
+                                    row3(m, azb[m % T3], avb[m % T3], lzb[m % T3], lvb[m % T3], bzb[m % T3], bvb[m % T3]);
+                                    if (m + T3 < DPL / 2) req3(m % T3, m + T3);
+                                    __builtin_amdgcn_sched_barrier(0);
+                                }
+                            } else if constexpr (!AFD && TCH3 > 0) {
 #pragma unroll
                                 for (int m0 = 0; m0 < DPL / 2; m0 += (TCH3 > 0 ? TCH3 : 1)) {
                                     constexpr int T3 = TCH3 > 0 ? TCH3 : 1;
