@@ -31,6 +31,13 @@ def group_build_counters(b):
     return tuple(out)
 
 
+def sampling_launches(b):
+    """launches of the sampling-phase build so far: a debug export of the library, not part of the ABI"""
+    fn = N.load_library().nm_debug_sampling_launches
+    fn.argtypes, fn.restype = [C.c_void_p], C.c_uint64
+    return int(fn(b._h))
+
+
 def run_engine(settings, logp, n_chains, x0, n_draws, chain_id_offset=0, dims_per_lane=0, waves_per_chain=0,
                lane_groups=0, grid_blocks=0, splits=(), lane_chains=0):
     """`splits`: draw counts at which the run is cut into separate launches; the pieces are concatenated."""
@@ -57,6 +64,45 @@ def run_oracle(O, settings, logp, n_chains, x0, n_draws, chain_id_offset=0, gpu_
     cfg = cfg or O.gpu_cfg(gpu_threads)
     return O.run(oracle_settings(O, settings), logp.kind, logp.dim, logp.params, cfg, n_chains, x0, n_draws,
                  chain_offset=chain_id_offset, n_threads=n_threads)
+
+
+def oracle_chains(oracle, s, logp, plan, n_chains, cfg=None):
+    """One oracle chain per engine chain, every chain through the same `plan`: a list of steps
+      ("set", x[chains][dim])                    set_position of every chain, status 0 expected
+      ("set", x[chains][dim], mask)              ... of the chains with mask[c] only (rows of the others are never read)
+      ("set", x[chains][dim], mask, expect)      ... with the status expect[c] expected of chain c (None: all chains, 0)
+      ("draw", k, ...)                           k draws of every chain whose last set_position succeeded (further entries are the engine's)
+    -> positions [draws][chains][dim], statistics [draws][chains], and per step a dict of the chains' state() after it: x, gx, stds, mean
+    [chains][dim], step_size [chains], ok [chains] (a chain that is not ok has no state: its rows are NaN, its draws' rows unwritten)."""
+    so = oracle_settings(oracle, s)
+    cfg = cfg or oracle.gpu_cfg(64)
+    n_draws = sum(step[1] for step in plan if step[0] == "draw")
+    pos = np.full((n_draws, n_chains, logp.dim), np.nan)
+    st = np.zeros((n_draws, n_chains), dtype=oracle.STATS_DTYPE)
+    states = [dict(x=np.full((n_chains, logp.dim), np.nan), gx=np.full((n_chains, logp.dim), np.nan), stds=np.full((n_chains, logp.dim), np.nan),
+                   mean=np.full((n_chains, logp.dim), np.nan), step_size=np.full(n_chains, np.nan), ok=np.zeros(n_chains, dtype=bool)) for _ in plan]
+    for c in range(n_chains):
+        ch = oracle.Chain(so, logp.kind, logp.dim, logp.params, cfg, chain_id=c)
+        t, ok = 0, False
+        for i, step in enumerate(plan):
+            if step[0] == "set":
+                x, mask, expect = (list(step[1:]) + [None, None])[:3]
+                if mask is None or mask[c]:
+                    rc = ch.set_position(x[c])
+                    assert rc == (0 if expect is None else expect[c]), (i, c, rc)
+                    ok = rc == 0
+            else:
+                for k in range(step[1]):
+                    if ok:
+                        pos[t + k, c], st[t + k, c], rc = ch.draw()
+                        assert rc == 0, (i, c, k, rc)
+                t += step[1]
+            if ok:
+                q = ch.state()
+                for f in ("x", "gx", "stds", "mean", "step_size"):
+                    states[i][f][c] = q[f]
+            states[i]["ok"][c] = ok
+    return pos, st, states
 
 
 def assert_bit_exact(pos_g, st_g, pos_o, st_o):

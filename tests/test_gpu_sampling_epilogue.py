@@ -3,14 +3,13 @@ merge_math_main).  Engine against oracle, bit for bit on positions and every sta
 that have a sampling build: dim 480 (8 doubles per lane), 600, 1000 (a partly filled tile) and 1024 (16 per lane).  The dims are the ones
 round 8 chose for the momentum refresh's block counts (a last round of 0 / 1, 16 / 17 and 5 .. 9 ChaCha blocks): the four-lanes-per-block
 form of that round was measured slower and is not in the build (profiles/r08_k2_sampling_epilogue_ab.txt); the cases stay."""
-import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
 import nuts_rs_amd as N
-from helpers import assert_bit_exact, oracle_settings
+from helpers import assert_bit_exact, oracle_settings, sampling_launches
 
 pytestmark = pytest.mark.gpu
 
@@ -18,12 +17,6 @@ N_CHAINS, NUM_TUNE = 6, 20
 LAUNCHES = [NUM_TUNE, 30, 30]          # the warm-up, then 60 further draws in two launches
 N_DRAWS = sum(LAUNCHES)
 DIMS = [(480, 8), (600, 16), (1000, 16), (1024, 16)]
-
-
-def sampling_launches(b):
-    fn = N.load_library().nm_debug_sampling_launches
-    fn.argtypes, fn.restype = [C.c_void_p], C.c_uint64
-    return int(fn(b._h))
 
 
 def make_logp(dens, dim):

@@ -1,14 +1,13 @@
 """The sampling-phase build of the wave-per-chain draw kernel (K_DRAW_SAMPLING: nuts_kernels.hpp `SAMPLING`, nuts_engine.hip
 `sampling_from`): the draws with an index > num_tune run on a kernel without the warm-up's code.  Whatever way a run is cut into
 launches, positions and every statistics field are the oracle's bits, and the debug counter shows which kernel served which draws."""
-import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
 import nuts_rs_amd as N
-from helpers import assert_bit_exact, assert_vectors_bit_exact, oracle_settings
+from helpers import assert_bit_exact, assert_vectors_bit_exact, oracle_chains, oracle_settings, sampling_launches
 
 pytestmark = pytest.mark.gpu
 
@@ -17,13 +16,6 @@ N_DRAWS = NUM_TUNE + N_POST                      # draw indices 0 .. 21: 12 .. 2
 # both ends of the (16 doubles, 1 wavefront) tiling, both ends of the (8, 1) tiling
 DIMS = [(513, 16), (1024, 16), (257, 8), (512, 8)]
 SPLITS = {"one_launch": [N_DRAWS], "launches_of_1": [1] * N_DRAWS, "launches_of_5": [5, 5, 5, 5, 2]}
-
-
-def sampling_launches(b):
-    """launches of the sampling-phase build so far: a debug export of the library, not part of the ABI"""
-    fn = N.load_library().nm_debug_sampling_launches
-    fn.argtypes, fn.restype = [C.c_void_p], C.c_uint64
-    return int(fn(b._h))
 
 
 def make_logp(dens, dim):
@@ -83,26 +75,6 @@ def test_boundary_in_every_position_bit_exact(oracle, dens, dim, dpl, split):
     assert (st_g["transformation_update_id"][NUM_TUNE + 1:] == -1).all()
 
 
-def oracle_chains(oracle, s, logp, plan):
-    """`plan`: a list of ("set", x[chains][dim]) / ("draw", k) steps on one oracle chain per chain -> positions, statistics of the draws"""
-    so = oracle_settings(oracle, s)
-    n_draws = sum(k for what, k in plan if what == "draw")
-    pos = np.empty((n_draws, N_CHAINS, logp.dim))
-    st = np.zeros((n_draws, N_CHAINS), dtype=oracle.STATS_DTYPE)
-    for c in range(N_CHAINS):
-        ch = oracle.Chain(so, logp.kind, logp.dim, logp.params, oracle.gpu_cfg(64), chain_id=c)
-        t = 0
-        for what, arg in plan:
-            if what == "set":
-                assert ch.set_position(arg[c]) == 0
-                continue
-            for _ in range(arg):
-                pos[t, c], st[t, c], rc = ch.draw()
-                assert rc == 0
-                t += 1
-    return pos, st
-
-
 def test_set_position_in_the_sampling_phase_goes_back_to_the_general_kernel(oracle):
     """set_position gives the chain a new mass matrix (from the gradient) and the step size of a new search: the next draw re-whitens,
     reports the transformation and replaces the step size — the general kernel's work.  After that draw the state is frozen again."""
@@ -123,7 +95,7 @@ def test_set_position_in_the_sampling_phase_goes_back_to_the_general_kernel(orac
     pos_d, st_d = b.draw_many(3)                           # ... also inside a launch: one general draw, two of the sampling build
     assert sampling_launches(b) == 3
     b.close()
-    pos_o, st_o = oracle_chains(oracle, s, logp, [("set", x0), ("draw", NUM_TUNE + 4), ("set", x1), ("draw", 5), ("set", x0), ("draw", 3)])
+    pos_o, st_o, _ = oracle_chains(oracle, s, logp, [("set", x0), ("draw", NUM_TUNE + 4), ("set", x1), ("draw", 5), ("set", x0), ("draw", 3)], N_CHAINS)
     pos_g, st_g = np.concatenate([pos_a, pos_b, pos_c, pos_d]), np.concatenate([st_a, st_b, st_c, st_d])
     assert_bit_exact(pos_g, st_g, pos_o, st_o)
     assert (st_b["transformation_update_id"] >= 0).all()   # the draw after set_position did have the general kernel's work to do

@@ -4,14 +4,13 @@ oracle, bit for bit on positions and every statistics field, on runs whose sampl
 test_gpu_sampling_epilogue.py never do (complete depth-4 trees only): tests of level 3 .. 5 (depth 5 and 6 trees), doublings that a test
 below the top ends, on the elementwise and the non-elementwise (funnel) path, and a partly filled tile (dim 600).  Each case first checks on
 the oracle's own statistics that its sampling draws still have that coverage."""
-import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
 import nuts_rs_amd as N
-from helpers import assert_bit_exact, oracle_settings
+from helpers import assert_bit_exact, oracle_settings, sampling_launches
 
 pytestmark = pytest.mark.gpu
 
@@ -26,12 +25,6 @@ CASES = {
     "iid_ta30": ("iid", 1024, 8, 0.3, 10, "early"),
     "diag600_ta95": ("diag", 600, 6, 0.95, 10, "deep"),
 }
-
-
-def sampling_launches(b):
-    fn = N.load_library().nm_debug_sampling_launches
-    fn.argtypes, fn.restype = [C.c_void_p], C.c_uint64
-    return int(fn(b._h))
 
 
 def make_logp(dens, dim):
