@@ -714,6 +714,130 @@ NM_HD MergeOut merge_math_main_impl(double a, double b, uint32_t w_lo, uint32_t 
 }
 static __host__ __device__ NM_DM_CALL MergeOut merge_math_main(double a, double b, uint32_t w_lo, uint32_t w_hi) { return merge_math_main_impl(a, b, w_lo, w_hi); }
 
+// ---- round 10: the sampling build decides its merges on an APPROXIMATE log-size (DESIGN §8 "Round 10") ------------------------------
+// A tree's log_size reaches no output: a merge hands the draw three bits (take, word consumed, fatal).  The sampling build carries an
+// approximation L~ of the log-size L the exact procedure would carry, |L~ - L| <= NM_MF_EPS_MAX, and merge_filter_impl decides the bits from
+// (a~, b~) wherever every exact pair within NM_MF_EPS_MAX of it gives the same bits; everywhere else (and for one merge in
+// 2^NM_MF_FORCE_BITS, so that the path below runs in every test) it answers NM_MF_UNDECIDED and the caller recomputes the exact pair from
+// the log of the draw's leaf weights (mf_fold / mf_fold_main) and calls merge_math / merge_math_main on it.
+// Portable arithmetic only (f32 fma polynomials, exponent insertion): the host runs the device's operation sequence, and
+// tests/cpp/merge_filter_check.hip measures the errors the derivation uses.
+constexpr int NM_MF_MAX_MD = 12;                  // deepest layout (maxdepth + extra_doublings) the bound below is derived for: 2 * 12 + 2 = 26 merges in a chain
+constexpr uint32_t NM_MF_FORCE_BITS = 8;          // a merge whose Bernoulli word has this many zero low bits takes the exact path whatever the filter says
+constexpr uint32_t NM_MF_UNDECIDED = 8u;          // flag bit 3 of merge_filter_impl's answer
+constexpr double NM_MF_ETA_E = 2e-7;              // mf_exp: relative error against exp_sl on every f32 in [-40, 0]            (measured 9.0e-8)
+constexpr double NM_MF_ETA_S = 2e-7;              // mf_log1p(mf_exp(-d)): absolute error against log1p_unit(exp_sl(-d))       (measured 1.1e-7)
+constexpr double NM_MF_EPS_MAX = 0x1p-16;         // >= 26 * (ETA_S + 2.2e-8 + 2^-22 + 2e-15)
+constexpr float NM_MF_KAPPA = 0x1p-14f;           // >= 2 EPS_MAX + 40 * 2^-24 + ETA_E + 2^-22 + 4 * 2^-24
+constexpr float NM_MF_DMIN = 0x1p-13f;            // |a~ - b~| below this: the order of a and b is not certain
+constexpr float NM_MF_EMIN = 0x1p-13f;            // b > a, exp(a - b) below this: p = 1 / (1 + e) is not certainly below 1, b not certainly below the total
+constexpr double NM_MF_MAG_MAX = 0x1p30;          // the LARGER operand beyond this in magnitude: the exact procedure's own rounding (2^-53 |total|) eats the budget.
+                                                  // (The smaller one is not bounded: within 40 of the larger it has its magnitude, further away it only has to be smaller.)
+NM_HD float mf_exp(float x) {                     // exp(x), x in [-40, 0]
+    const float nf = __builtin_rintf(x * 1.44269502e+00f);
+    float r = __builtin_fmaf(nf, -0.693145751953125f, x);             // (ln 2 to 16 bits: nf * hi is exact)
+    r = __builtin_fmaf(nf, -1.42860677e-06f, r);
+    float p = 0.0013941146899014711f;
+    p = __builtin_fmaf(p, r, 0.008375156670808792f);
+    p = __builtin_fmaf(p, r, 0.04166635125875473f);
+    p = __builtin_fmaf(p, r, 0.16666415333747864f);
+    p = __builtin_fmaf(p, r, 0.5f);
+    p = __builtin_fmaf(p, r, 1.0f);
+    p = __builtin_fmaf(p, r, 1.0f);                                    // [0.70, 1.42]
+    return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, p) + ((uint32_t)(int)nf << 23));      // * 2^nf, nf in [-58, 0]
+}
+NM_HD float mf_log1p(float y) {                   // ln(1 + y), y in [0, 1]
+    float p = -0.0031760570127516985f;
+    p = __builtin_fmaf(p, y, 0.019542526453733444f);
+    p = __builtin_fmaf(p, y, -0.056373611092567444f);
+    p = __builtin_fmaf(p, y, 0.10543623566627502f);
+    p = __builtin_fmaf(p, y, -0.1526966691017151f);
+    p = __builtin_fmaf(p, y, 0.1966327428817749f);
+    p = __builtin_fmaf(p, y, -0.24951615929603577f);
+    p = __builtin_fmaf(p, y, 0.33329710364341736f);
+    p = __builtin_fmaf(p, y, -0.49999892711639404f);
+    p = __builtin_fmaf(p, y, 1.0f);
+    return p * y;
+}
+// flags: merge_math_impl's bits 0 .. 2 (bit 2 never set), or NM_MF_UNDECIDED alone.  total: max(a, b) + s~(|a - b|), within
+// ETA_S + 2.2e-8 + 2^-53 (|total| + 1) of the logaddexp of (a, b) when both are finite and at most NM_MF_MAG_MAX in magnitude.
+// With u = w_hi 2^-32 the chain's word W = w 2^-64 lies in [u, u + 2^-32), and the exact procedure takes iff W + 2^-64 <= p, where
+// p = exp(b - a) = e (main tree, b < a), p = exp(b - total) = e / (1 + e) (a > b) or 1 / (1 + e) (a < b), e = exp(-|a - b|).  So, free of
+// a division: take if (u + 2^-32) den (1 + kappa) < q, keep if u den (1 - kappa) > q, undecided between the two.
+NM_HD MergeOut merge_filter_impl(double a, double b, uint32_t is_main, uint32_t w_lo, uint32_t w_hi) {
+    const double d = a - b;
+    const bool a_gt = d > 0.0;
+    const double mx = a_gt ? a : b;                                   // (a NaN or an infinite operand: undecided below)
+    const float ad = __builtin_fabsf((float)d);
+    const float e = mf_exp(-__builtin_fminf(ad, 40.0f));              // (a NaN difference: -40; the answer is undecided below)
+    const float s = mf_log1p(e);
+    // (the smaller operand may be anything below, -inf included: beyond |a - b| = 40 it only has to be smaller.  A NaN makes `ad` NaN, +inf the maximum infinite.)
+    const bool in_range = __builtin_fabs(mx) <= NM_MF_MAG_MAX && ad >= NM_MF_DMIN;
+    const float u = (float)w_hi * 0x1p-32f;
+    const float den = is_main ? 1.0f : 1.0f + e;
+    const float q = a_gt ? e : 1.0f;
+    const float ud = u * den;
+    const bool take = __builtin_fmaf(ud, 1.0f + NM_MF_KAPPA, 0x1p-30f) < q;
+    const float udk = ud * (1.0f - NM_MF_KAPPA);
+    const bool keep = udk > q;
+    const bool forced = (w_lo & ((1u << NM_MF_FORCE_BITS) - 1u)) == 0u;
+    // a > b: b < a <= self for certain, p <= e < 1.  a < b: into the main tree `ge` decides (take, no word drawn); into a sub-tree e >= EMIN
+    // keeps p = 1 / (1 + e) and the total's excess over b (>= ln(1 + e)) clear of 1 and of the total's rounding.
+    const bool ge_main = is_main && !a_gt;
+    const bool bern = (take || keep) && (a_gt || e >= NM_MF_EMIN);
+    const bool decided = in_range && !forced && (ge_main || bern);
+    MergeOut o;
+    o.total = mx + (double)s;
+    o.flags = decided ? (ge_main ? 1u : (take ? 3u : 2u)) : NM_MF_UNDECIDED;
+    return o;
+}
+// (Inlined at the three merge sites.  As full builds against the parent commit on K2: inlined +2.8 % / +3.7 %, out of line with merge_math's calling
+// shape +1.0 % / +1.3 % — profiles/r10_k2_merge_filter_ab.txt, sections 2 and 2b.)
+// logaddexp as merge_math_impl evaluates it (its first half: the same operation sequence, the same bits — tests/cpp/merge_filter_check.hip)
+NM_HD double logaddexp_sl(double a, double b) {
+    const double diff = a - b;
+    const double e = exp_sl(diff > 0. ? -diff : diff);
+    const double lp = log1p_unit(e);
+    double total = (diff > 0. ? a : b) + lp;
+    total = (diff > 0. || diff < 0.) ? total : diff;
+    return a == b ? a + 0x1.62e42fefa39efp-1 : total;
+}
+// The exact log-size of a (sub-)tree is a function of its leaves' weights alone, folded in the reference's order:
+//   fold(first, 1) = w[first],   fold(first, 2 m) = logaddexp(fold(first, m), fold(first + m, m))          (a sub-tree of `other`)
+//   main(0) = 0.0,   main(j + 1) = logaddexp(main(j), fold(2^j - 1, 2^j))                                  (the main tree after j + 1 doublings)
+// over the log w[2^depth - 1 + n] = weight of leaf n of the doubling at `depth` (a discarded doubling is overwritten by the next one at its depth).
+NM_HD double mf_fold(const double* w, uint32_t first, uint32_t count) {       // count: a power of two <= 2^NM_MF_MAX_MD
+    double st[NM_MF_MAX_MD + 1];
+    int sp = 0;
+    for (uint32_t i = 0; i < count; ++i) {
+        double v = w[first + i];
+        for (uint32_t c = i; c & 1u; c >>= 1) v = logaddexp_sl(st[--sp], v);
+        st[sp++] = v;
+    }
+    return st[0];
+}
+NM_HD double mf_fold_main(const double* w, uint32_t depth) {
+    double l = 0.0;
+    for (uint32_t j = 0; j < depth; ++j) l = logaddexp_sl(l, mf_fold(w, (1u << j) - 1u, 1u << j));
+    return l;
+}
+// The exact path of an undecided merge (cold, out of line): the exact pair from the wave's leaf log, then today's routine on it.  Sub-tree:
+// a = fold(first, count), b = fold(first + count, count); main tree: a = main(depth), b = fold(count - 1, count), count = 2^depth.
+// One lane counts the visit in the u64 behind the log (nm_debug_merge_exact_paths): thread 0 of the block, which is one wavefront wherever a sampling
+// build exists (nuts_kernels.hpp has_sampling_build: W == 1; merge_weights asserts it).
+static __device__ __noinline__ MergeOut merge_exact(double* log, uint32_t counter_at, uint32_t first, uint32_t count, uint32_t is_main, uint32_t w_lo, uint32_t w_hi) {
+    first = (uint32_t)__builtin_amdgcn_readfirstlane((int)first);
+    count = (uint32_t)__builtin_amdgcn_readfirstlane((int)count);
+    is_main = (uint32_t)__builtin_amdgcn_readfirstlane((int)is_main);
+    if (threadIdx.x == 0) reinterpret_cast<unsigned long long*>(log)[counter_at] += 1ull;
+    if (is_main) {
+        const double a = mf_fold_main(log, (uint32_t)__builtin_ctz(count));
+        return merge_math_main(a, mf_fold(log, count - 1u, count), w_lo, w_hi);
+    }
+    const double a = mf_fold(log, first, count);
+    return merge_math(a, mf_fold(log, first + count, count), 0u, w_lo, w_hi);
+}
+
 // exp(x) - 1 for the isokinetic momentum refresh (reference f64::exp_m1, transformed_hamiltonian.rs:800-801): the same
 // operation sequence as oracle/nmo_math.hpp det_expm1 (Taylor series to x^14 for |x| <= 0.35, else exp(x) - 1)
 template <bool INL>

@@ -1872,19 +1872,37 @@ NM_DEV void lr_commit_update(ChainCtx<DPL, W, Dens>& C) {
 struct CandRef { int slot; double logp, ke; int64_t idx; };   // slot: -3 live in E, -2 live in O, -1 initial point, >=0 pool
 enum TreeStop { STOP_NONE = 0, STOP_TURNING = 1, STOP_DIVERGING = 2, STOP_FATAL = 3 };
 
+// The sampling build's log of leaf weights (round 10; dev_math.hpp mf_fold): behind the tree's slots of this wave's scratch, entry
+// 2^depth - 1 + n = weight of leaf n of the doubling at `depth`, then (at 2^layout_md) the u64 count of exact-path merges.  One 8-byte
+// vector store, every lane the same address and value.
+template <int DPL, int W, class Dens>
+NM_DEV void leaf_log_put(const ChainCtx<DPL, W, Dens>& C, uint32_t idx, double w) {
+    v2u q;
+    q.x = (unsigned)__double2loint(w); q.y = (unsigned)__double2hiint(w);
+    __builtin_amdgcn_raw_buffer_store_b64(q, C.rs, (int)(idx * 8u), C.soS(num_sslots(C.maxdepth_cfg)), 0);
+}
 // multinomial merge weights (reference merge_into, src/nuts.rs:172-207).  Returns take_B.
-// MAIN1: the merge into the main tree with one exp (dev_math.hpp merge_math_main; is_main must be true) — the sampling build's top-level site.
-template <int DPL, int W, class Dens, bool MAIN1 = false>
-NM_DEV bool merge_weights(ChainCtx<DPL, W, Dens>& C, double a_log_size, double b_log_size, bool is_main, double& total, bool& fatal) {
+// SMP: the sampling build's sites (round 10).  a_log_size / b_log_size / total are approximations there, merge_filter_impl decides take / word
+// consumed from them, and an undecided merge is redone exactly from the leaf log: (log_first, log_count) name the two sub-trees' leaves
+// (dev_math.hpp merge_exact), and `total` is then the exact one.
+template <int DPL, int W, class Dens, bool SMP = false>
+NM_DEV bool merge_weights(ChainCtx<DPL, W, Dens>& C, double a_log_size, double b_log_size, bool is_main, double& total, bool& fatal,
+                          [[maybe_unused]] uint32_t log_first = 0, [[maybe_unused]] uint32_t log_count = 0) {
     NM_MARK(C, 13)
     // the whole of merge_into's arithmetic in one branch-free routine (dev_math.hpp merge_math).  The chain's next u64 is read here and
     // consumed only if the routine says random_bool drew it; refilling the word cache early changes nothing (it is a window onto the stream).
     if (!C.rng.has(2)) C.rng.refill();
     const uint32_t off_ = (uint32_t)(C.rng.pos - C.rng.base);
-    if constexpr (MAIN1) {
-        const MergeOut mm = merge_math_main(a_log_size, b_log_size, C.rng.cache[off_], C.rng.cache[off_ + 1]);
+    if constexpr (SMP) {
+        static_assert(W == 1, "merge_exact counts its visits with thread 0 of a one-wavefront block, and the leaf log is one per block");
+        const uint32_t w_lo = C.rng.cache[off_], w_hi = C.rng.cache[off_ + 1];
+        MergeOut mm = merge_filter_impl(a_log_size, b_log_size, is_main ? 1u : 0u, w_lo, w_hi);
+        uint32_t mmf = (uint32_t)__builtin_amdgcn_readfirstlane((int)mm.flags);
+        if (__builtin_expect((mmf & NM_MF_UNDECIDED) != 0u, 0)) {
+            mm = merge_exact(C.sslot(num_sslots(C.maxdepth_cfg)), 1u << C.maxdepth_cfg, log_first, log_count, is_main ? 1u : 0u, w_lo, w_hi);
+            mmf = (uint32_t)__builtin_amdgcn_readfirstlane((int)mm.flags);
+        }
         total = uniform_f64(mm.total);
-        const uint32_t mmf = (uint32_t)__builtin_amdgcn_readfirstlane((int)mm.flags);
         C.rng.pos += (uint64_t)(mmf & 2u);
         if (mmf & 4u) fatal = true;
         return (mmf & 1u) != 0;
@@ -2060,7 +2078,8 @@ NM_DEV int ring_to_pool(ChainCtx<DPL, W, Dens>& C, uint32_t& used, int ring_lane
 
 // nuts::draw (reference src/nuts.rs:281-388).  On entry the chain's current point is in its slots P_*.
 // On exit, if R.chosen.slot >= 0, zc holds the chosen point's z.
-// SAMPLING (the sampling-phase build, see `adapt`): the merge into the main tree with one exp (round 8, dev_math.hpp merge_math_main).
+// SAMPLING (the sampling-phase build, see `adapt`): every merge is decided by dev_math.hpp merge_filter_impl on approximate log-sizes, the leaves' weights are
+// logged, and an undecided merge is redone exactly from the log (round 10; the exact merge into the main tree is round 8's merge_math_main).
 template <int DPL, int W, class Dens, bool SAMPLING = false>
 NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col, DrawResult& R, Tile<DPL>& zc) {
     const nm_settings& s = C.P.s;
@@ -2184,7 +2203,7 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
         o_is_edge = false;               // O is about to be overwritten; set again only by a successful merge
 
         // divergence test + collector for a fresh leaf (transformed_hamiltonian.rs:590-612); returns -energy_error
-#define NM_LEAF_ACCOUNT(START, PT, WOUT)                                                                  \
+#define NM_LEAF_ACCOUNT(START, PT, WOUT, LOGIDX)                                                          \
         {                                                                                                 \
             const double energy_ = (PT).ke - ((PT).logp + logdet);                                        \
             const double err_ = energy_ - e0;                                                             \
@@ -2208,6 +2227,7 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
             } else {                                                                                      \
                 col.register_ok(energy_);                                                                 \
                 WOUT = -err_;                                                                             \
+                if constexpr (SAMPLING) leaf_log_put(C, (uint32_t)(LOGIDX), WOUT);                        \
             }                                                                                             \
         }
 
@@ -2290,7 +2310,7 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
             if constexpr (NOG) leapfrog<DPL, W, Dens, 2, 2>(C, E, O, epsilon, (Tile<DPL>*)nullptr, (Tile<DPL>*)nullptr, C.edge_g(0), gsh);
             else leapfrog<DPL, W, Dens, 2>(C, E, O, epsilon, (Tile<DPL>*)nullptr, (Tile<DPL>*)nullptr);
             O.idx = edge_idx + (int64_t)sign;
-            NM_LEAF_ACCOUNT(E, O, sub_log_size)
+            NM_LEAF_ACCOUNT(E, O, sub_log_size, 0)
             NM_MARK(C, 27)
             sub_cand = {-2, O.logp, O.ke, O.idx};
         } else {
@@ -2322,7 +2342,7 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                 leapfrog<DPL, W, Dens, 2>(C, O, E, epsilon, (Tile<DPL>*)nullptr, (Tile<DPL>*)nullptr);
                 NM_MARK(C, 17)
                 E.idx = edge_idx + (int64_t)sign * (int64_t)(n + 1);
-                NM_LEAF_ACCOUNT(O, E, wE)
+                NM_LEAF_ACCOUNT(O, E, wE, nleaf - 1 + n)
                 if (stop != STOP_NONE) break;
                 // ---- odd leaf n + 1
                 NM_MARK(C, 18)
@@ -2331,7 +2351,7 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                 leapfrog<DPL, W, Dens, 2>(C, E, O, epsilon, (Tile<DPL>*)nullptr, (Tile<DPL>*)nullptr);
                 NM_MARK(C, 19)
                 O.idx = edge_idx + (int64_t)sign * (int64_t)(n + 2);
-                NM_LEAF_ACCOUNT(E, O, wO)
+                NM_LEAF_ACCOUNT(E, O, wO, nleaf + n)
                 if (stop != STOP_NONE) break;
                 const uint64_t nn = n + 1;
                 const int t = (int)__builtin_ctzll(~nn);           // trailing ones of the odd leaf: merges up to level t
@@ -2475,7 +2495,7 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                 // ---- level-1 merge: A = {E}, B = {O}
                 {
                     double total;
-                    const bool take = merge_weights(C, wE, wO, false, total, fatal);
+                    const bool take = merge_weights<DPL, W, Dens, SAMPLING>(C, wE, wO, false, total, fatal, (uint32_t)(nleaf - 1 + n), 1u);
                     sub_cand = take ? CandRef{-2, O.logp, O.ke, O.idx} : CandRef{-3, E.logp, E.ke, E.idx};
                     sub_log_size = total;
                     if (fatal) { stop = STOP_FATAL; break; }
@@ -2484,7 +2504,7 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                 for (int k = 2; k <= t; ++k) {
                     const PendEntry A = C.pend[k - 1];
                     double total;
-                    const bool take = merge_weights(C, A.log_size, sub_log_size, false, total, fatal);
+                    const bool take = merge_weights<DPL, W, Dens, SAMPLING>(C, A.log_size, sub_log_size, false, total, fatal, (uint32_t)(nleaf + nn - (1ull << k)), 1u << (k - 1));
                     if (take) {
                         used &= ~(1u << A.cand_slot);
                     } else {
@@ -2526,7 +2546,7 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                 leapfrog<DPL, W, Dens, 2>(C, O, E, epsilon, (Tile<DPL>*)nullptr, (Tile<DPL>*)nullptr);
                 NM_MARK(C, 17)
                 E.idx = edge_idx + (int64_t)sign * (int64_t)(n + 1);
-                NM_LEAF_ACCOUNT(O, E, wE)
+                NM_LEAF_ACCOUNT(O, E, wE, 0)
                 // BATCH: what the single resolve_chunk site below has to do for this pair — the merges closing at lanes < rs_nl
                 // and levels 1..rs_kl at lane rs_nl (a divergence: the merges that closed before the divergent leaf drew their
                 // words, src/nuts.rs:131-136; the even leaf closes nothing, so both leaves of a pair give lane n - 1)
@@ -2547,7 +2567,7 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
                 leapfrog<DPL, W, Dens, 2>(C, E, O, epsilon, (Tile<DPL>*)nullptr, (Tile<DPL>*)nullptr);
                 NM_MARK(C, 19)
                 O.idx = edge_idx + (int64_t)sign * (int64_t)(n + 2);
-                NM_LEAF_ACCOUNT(E, O, wO)
+                NM_LEAF_ACCOUNT(E, O, wO, 0)
                 if constexpr (BATCH) {
                     if (stop == STOP_DIVERGING && (n & 63) != 0) {
                         rs_do = true; rs_nl = (int)(n & 63) - 1; rs_kl = (int)__builtin_ctz(~(unsigned)rs_nl);
@@ -2720,7 +2740,7 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
         if (check) turning = top_level_turning();
         NM_MARK(C, 26)
         double total;
-        const bool take = merge_weights<DPL, W, Dens, SAMPLING>(C, log_size, sub_log_size, true, total, fatal);
+        const bool take = merge_weights<DPL, W, Dens, SAMPLING>(C, log_size, sub_log_size, true, total, fatal, 0u, (uint32_t)nleaf);
         if (fatal) break;
         if (take) {
             if (mc.slot >= 0) used &= ~(1u << mc.slot);
