@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define NM_ABI_VERSION 16
+#define NM_ABI_VERSION 17
 
 typedef enum nm_status {
     NM_OK = 0,
@@ -234,6 +234,18 @@ typedef struct nm_logp_spec {
  * transformation (bit 0: adaptation = NM_ADAPT_LOW_RANK, `LowRankNutsSettings`) and into those with the non-Euclidean trajectory kinds
  * and MCLMC (bit 1); build_density_module(..., variants=("low_rank", "kinetic")).  Without them the engine answers
  * NM_ERR_UNSUPPORTED for those settings with this module.
+ * Expansion (optional; `CpuLogpFunc::expand_vector`, src/math/cpu_math.rs:892-899: what the user reads instead of the unconstrained point —
+ * constrained parameters, deterministics, the centred form of a non-centred model): a density that defines the two static members
+ *     static NM_HD  uint64_t expanded_dim(uint64_t dim, const double* params, uint64_t n_params);     length of the expanded vector (host too)
+ *     static NM_DEV double   expand_element(const double* params, int dim, const double* x, int j);   element j of the expansion of x[0 .. dim)
+ * has its draws expanded on the device (nm_draw_outputs.d_expanded, nm_engine_expand), and its module exports nm_module_expand /
+ * nm_module_expanded_dim, which the engine looks up by name.  A density that defines neither expands to the position itself.  The
+ * expansion is written per output element: a function of (params, x, j) alone, whatever the kernel's mapping of threads to rows (x may
+ * point to LDS or to global memory; params is the DEVICE copy in expand_element and the HOST array in expanded_dim).  Lanes of a wavefront
+ * work on different rows there: use the per-lane nm::xexp / xlog / xlog1p, not the wave-uniform nm::uexp / ulog of `eval`
+ * (tests/user_density/my_expanding_normal.hpp).  DEPARTURE from the reference: expand_vector receives the chain's generator there; here an
+ * expansion is deterministic — it never sees or advances a chain's random stream, and generated quantities that need randomness are out
+ * of scope (no density the reference ships uses that argument).
  * ------------------------------------------------------------------------------------------- */
 /* The tiling the engine uses for `dim` (requested_* = 0: automatic): doubles per lane and waves per chain. */
 nm_status nm_pick_tiling(uint64_t dim, uint64_t requested_dims_per_lane, uint64_t requested_waves_per_chain,
@@ -287,6 +299,9 @@ typedef struct nm_draw_stats {
  *   store_transformed   -> d_transformed_position, d_transformed_gradient
  *   store_mass_matrix   -> d_mass_matrix_inv, d_transformation_mu   (event rows)
  *   store_divergences   -> d_divergence_start, d_divergence_start_gradient, d_divergence_end   (event rows)
+ * d_expanded needs d_positions (NM_ERR_INVALID_ARG without) and must not overlap it (NM_ERR_INVALID_ARG), except that a density whose
+ * expansion is the identity may name the same buffer for both: nothing is copied then.  Rows of failed chains are expanded from whatever
+ * their position rows hold (NaN through the *_to_host calls).  The expansion never touches a chain's random stream.
  * Event rows are written only on the draws where the event happens (stats.transformation_update_id >= 0, resp.
  * stats.diverging != 0); other rows are left untouched.  `divergence_momentum` is always None on this path
  * (start_momentum: None, src/dynamics/transformed_hamiltonian.rs:567, :596) and has no buffer. */
@@ -304,7 +319,10 @@ typedef struct nm_draw_outputs {
     double*        d_mass_matrix_eigvals;     /* MatrixStats.mass_matrix_eigvals (low_rank.rs:232-243): lambda^(1/2) of the low-rank
                                                  part, NaN beyond num_eigenvalues; event row (NM_ADAPT_LOW_RANK only;
                                                  d_mass_matrix_inv then carries MatrixStats.mass_matrix_stds) */
-    uint64_t       reserved[5];
+    double*        d_expanded;                /* [n_draws][n_chains][expanded dim]: `CpuLogpFunc::expand_vector` of every recorded draw (the
+                                                 second element of Chain::expanded_draw's tuple, src/chain.rs:201), computed on the device from
+                                                 d_positions — which it needs — in a pass after the draw launches; nm_engine_expanded_dim columns */
+    uint64_t       reserved[4];
 } nm_draw_outputs;
 
 typedef struct nm_engine nm_engine;
@@ -379,7 +397,8 @@ nm_status nm_init_positions_uniform_at(uint64_t seed, uint64_t chain_id_offset, 
 nm_status nm_engine_draw(nm_engine* e, uint64_t n_draws, double* d_positions, nm_draw_stats* d_stats);
 
 /* `Chain::expanded_draw` x n_draws (reference src/chain.rs:190-204): nm_engine_draw plus the vector-valued
- * statistics selected by the non-NULL pointers of `out`.  Asynchronous variant: returns after enqueueing. */
+ * statistics selected by the non-NULL pointers of `out` and, with out->d_expanded, the expanded draws (one streaming pass over
+ * the rows of this call, enqueued behind its draw launches).  Asynchronous variant: returns after enqueueing. */
 nm_status nm_engine_draw_ex(nm_engine* e, uint64_t n_draws, const nm_draw_outputs* out);
 nm_status nm_engine_draw_ex_async(nm_engine* e, uint64_t n_draws, const nm_draw_outputs* out);
 
@@ -400,6 +419,18 @@ nm_status nm_host_unregister(void* h_ptr);
 /* nm_engine_draw_ex with HOST destinations: the pointers of `h_out` are host arrays of the same shapes; event
  * rows that were not written read as NaN. */
 nm_status nm_engine_draw_ex_to_host(nm_engine* e, uint64_t n_draws, const nm_draw_outputs* h_out);
+
+/* The expanded vector (`CpuLogpFunc::expand_vector`, reference src/math/cpu_math.rs:892-899; `Math::expand_vector`, src/math/math.rs:63-67).
+ * nm_logp_expanded_dim: its length for a density — dim for the densities that expand to the position itself (iid / diagonal / full
+ * normal, funnel, NM_LOGP_HOST_CALLBACK, modules without an expansion), 10 for NM_LOGP_EIGHT_SCHOOLS ((mu, tau, theta[8]) with
+ * tau = exp(log tau), theta_i = mu + tau theta~_i), a module's own answer (the module is loaded for the call).  Pure host, no device.
+ * nm_engine_expanded_dim: the same for an engine's density.
+ * nm_engine_expand: the expansion of n_rows rows the caller already holds, d_positions [n_rows][dim] -> d_expanded [n_rows][expanded dim],
+ * asynchronously on the engine's stream (the kernel the draw calls run for d_expanded).  The buffers must not overlap; for a density
+ * whose expansion is the identity it is a device-to-device copy, and nothing at all when the two pointers are equal. */
+nm_status nm_logp_expanded_dim(const nm_logp_spec* logp, uint64_t* expanded_dim);
+uint64_t  nm_engine_expanded_dim(const nm_engine* e);
+nm_status nm_engine_expand(nm_engine* e, uint64_t n_rows, const double* d_positions, double* d_expanded);
 
 /* ---------------------------------------------------------------------------------------------
  * The low-rank transformation (NM_ADAPT_LOW_RANK; reference `LowRankMassMatrix`, src/transform/low_rank.rs:95-186):

@@ -255,6 +255,8 @@ public:
     ChainBatch& operator=(const ChainBatch&) = delete;
 
     uint64_t dim() const { return dim_; }
+    // length of an expanded draw (`CpuLogpFunc::expand_vector`, reference src/math/cpu_math.rs:892-899): the columns of nm_draw_outputs::d_expanded
+    uint64_t expanded_dim() const { return nm_engine_expanded_dim(h_); }
     uint64_t num_chains() const { return n_; }
     nm_engine* handle() { return h_; }
 
@@ -296,7 +298,8 @@ public:
     void draw_many(uint64_t n_draws, double* positions, nm_draw_stats* stats) {
         check(nm_engine_draw_to_host(h_, n_draws, positions, stats));
     }
-    // `Chain::expanded_draw` x n_draws: host pointers of `out` select the vector statistics (nm_draw_outputs)
+    // `Chain::expanded_draw` x n_draws: host pointers of `out` select the vector statistics (nm_draw_outputs); d_expanded
+    // ([n_draws][n_chains][expanded_dim()], needs d_positions) receives the expanded draws
     void expanded_draw_many(uint64_t n_draws, const nm_draw_outputs& host_out) {
         check(nm_engine_draw_ex_to_host(h_, n_draws, &host_out));
     }

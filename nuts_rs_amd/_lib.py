@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "nm_lowrank_compute_update", "nm_lowrank_test_spd_mean", "nm_lowrank_test_estimate_mass_matrix", "nm_engine_set_lowrank_estimator_place", "nm_engine_lowrank_device_updates", "nm_lowrank_block_twin", "nm_lowrank_test_block_device", "nm_engine_set_transform", "nm_engine_get_lowrank", "nm_engine_lowrank_max_rank",
     "nm_lowrank_transform_batch", "nm_engine_set_positions_masked", "nm_engine_init_positions_retry",
     "nm_init_positions_uniform_at", "nm_engine_tile_launches", "nm_engine_lockstep_launches", "nm_engine_reduce_order", "nm_engine_host_logp_calls", "nm_pooled_partials", "nm_pooled_exchange", "nm_pooled_finish", "nm_pooled_last_error",
+    "nm_logp_expanded_dim", "nm_engine_expanded_dim", "nm_engine_expand",
     # the per-vector `Math` seam
     "nm_math_create", "nm_math_destroy", "nm_math_dim", "nm_math_threads", "nm_math_last_error", "nm_vec_new", "nm_vec_free", "nm_vec_read_from_slice", "nm_vec_write_to_slice", "nm_vec_copy_into", "nm_vec_fill_array", "nm_vec_array_recip", "nm_vec_axpy_out", "nm_vec_axpy", "nm_vec_array_mult", "nm_vec_array_vector_dot", "nm_vec_scalar_prods3", "nm_vec_array_gaussian", "nm_vec_array_update_variance", "nm_vec_array_update_var_inv_std_draw_grad", "nm_vec_array_update_var_inv_std_grad", "nm_vec_array_update_var_inv_std_draw", "nm_vec_array_sum_ln", "nm_vec_array_all_finite", "nm_vec_logp_array", "nm_vec_sq_norm_sum", "nm_vec_std_norm_flow", "nm_vec_std_norm_grad_flow", "nm_vec_esh_momentum_update", "nm_vec_array_normalize",
 ]
@@ -86,14 +87,15 @@ STATS_DTYPE = np.dtype([
     ("transformation_update_id", "<i8"), ("num_eigenvalues", "<u8"), ("energy_change", "<f8"), ("average_step_size", "<f8"),
 ])
 
-# nm_draw_outputs: the draws, the scalar statistics and the vector-valued statistics (reference stat names)
+# nm_draw_outputs: the draws, the scalar statistics, the vector-valued statistics (reference stat names; every entry has dim columns) and
+# d_expanded, the expanded draws ([n_draws][n_chains][expanded dim]; `CpuLogpFunc::expand_vector` of every recorded position)
 VECTOR_STATS = ("gradient", "transformed_position", "transformed_gradient", "mass_matrix_inv", "transformation_mu",
                 "divergence_start", "divergence_start_gradient", "divergence_end", "mass_matrix_eigvals")
 
 
 class NmDrawOutputs(C.Structure):
     _fields_ = ([("d_positions", C.c_void_p), ("d_stats", C.c_void_p)] + [("d_" + k, C.c_void_p) for k in VECTOR_STATS]
-                + [("reserved", C.c_uint64 * 5)])
+                + [("d_expanded", C.c_void_p), ("reserved", C.c_uint64 * 4)])
 
 
 # nm_lowrank_estimator_fn
@@ -216,6 +218,10 @@ def load():
         fn.restype = u64
     L.nm_engine_host_logp_calls.argtypes = [vp]
     L.nm_engine_host_logp_calls.restype = u64
+    L.nm_logp_expanded_dim.argtypes = [C.POINTER(NmLogpSpec), C.POINTER(u64)]
+    L.nm_engine_expanded_dim.argtypes = [vp]
+    L.nm_engine_expanded_dim.restype = u64
+    L.nm_engine_expand.argtypes = [vp, u64, vp, vp]
     pd, pu = C.POINTER(dbl), C.POINTER(u64)
     L.nm_math_create.argtypes = [C.POINTER(NmLogpSpec), C.POINTER(vp)]
     L.nm_math_destroy.argtypes = [vp]

@@ -21,15 +21,16 @@ UNITS = ["kern_tile_mvn_prec.hip", "kern_tile_mvn_diag.hip", "kern_lockstep.hip"
          "kern_kin_diag_normal.hip@small", "kern_kin_funnel.hip@large", "kern_kin_funnel.hip@small", "kern_kin_host_cb.hip@large", "kern_kin_host_cb.hip@small", "kern_lane.hip",
          "kern_lane_kin.hip", "kern_iid_normal.hip@large", "kern_iid_normal.hip@small", "kern_diag_normal.hip@large", "kern_diag_normal.hip@small", "kern_funnel.hip@large",
          "kern_funnel.hip@small", "kern_host_cb.hip@large", "kern_host_cb.hip@small", "nuts_engine.hip", "kern_cluster.hip", "kern_cluster_kin.hip", "kern_eight_schools.hip@inl",
-         "kern_lr_eight_schools.hip@inl", "kern_kin_eight_schools.hip@inl", "math_seam.hip", "probe_bw.hip", "pooled_reduce.hip", "lowrank_device.hip", "lowrank_host.cpp"]
+         "kern_lr_eight_schools.hip@inl", "kern_kin_eight_schools.hip@inl", "math_seam.hip", "probe_bw.hip", "pooled_reduce.hip", "lowrank_device.hip", "kern_expand.hip@inl", "lowrank_host.cpp"]
 # (lowrank_host.cpp holds both ISA builds of the host estimator in ONE translation unit: per-function target attributes, see there)
 # Variants of a unit ("file@variant": its own object, the flags below).  A density's one-chain kernels are TWO units from one source
 # (nuts_launch.hpp NM_TU_PART): "small" = the tilings of <= 4 doubles per lane + the small-chain kernels with EVERY special function inlined — no
 # out-of-line device call (fourth incident; the scan below rejects an s_swappc_b64 there) —, "large" = the 8- and 16-doubles tilings with
-# the calls (inlined they cost K2 11 %); "inl" = a unit that only has small tilings (8 schools).
+# the calls (inlined they cost K2 11 %); "inl" = a unit that only has small tilings (8 schools), or whose lanes work on different rows
+# (kern_expand.hip, the expansion pass: nuts_expand.hpp).
 VARIANT_FLAGS = {"": [], "small": ["-DNM_TU_PART=1", "-DNM_DETMATH_INLINE=1"], "large": ["-DNM_TU_PART=2"], "inl": ["-DNM_DETMATH_INLINE=1"]}
 NO_CALL_VARIANTS = ("small", "inl")
-HEADERS = ["nuts_kernels.hpp", "nuts_launch.hpp", "dev_math.hpp", "detmath_tables.hpp", "zig_tables.hpp", "nuts_group.hpp", "nuts_group_impl.hpp", "nuts_tile.hpp", os.path.join("..", "..", "include", "nuts_amd.h")]
+HEADERS = ["nuts_kernels.hpp", "nuts_launch.hpp", "dev_math.hpp", "detmath_tables.hpp", "zig_tables.hpp", "nuts_group.hpp", "nuts_group_impl.hpp", "nuts_tile.hpp", "nuts_expand.hpp", os.path.join("..", "..", "include", "nuts_amd.h")]
 # -ffp-contract=off: FMAs only where the reference writes mul_add
 # -Wno-pass-failed: "loop not unrolled" remarks of the matrix-core kernel's partially unrolled product loops (a diagnostic only)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-pass-failed"]

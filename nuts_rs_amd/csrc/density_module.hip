@@ -8,6 +8,7 @@
 // Optional, for dim <= 64: -DNM_MODULE_GROUP_DENSITY=<template name> -DNM_MODULE_GS=<8|16|32> adds the density's group form
 // (several chains per wavefront, nuts_group.hpp): `template <class L> struct Name` written against L = Lanes.
 #include "nuts_launch.hpp"
+#include "nuts_expand.hpp"
 #ifdef NM_MODULE_LANE_DENSITY
 #include "nuts_lane.hpp"      // (before the user's header: its lane form is written against nm::lane)
 #endif
@@ -56,6 +57,27 @@ static hipError_t module_lane_t(int query, bool tune, const KParams& P, const La
 #ifndef NM_MODULE_VARIANTS
 #define NM_MODULE_VARIANTS 0          // bit 0: the kernels with the low-rank transformation (LowRankNutsSettings), bit 1: the non-Euclidean
 #endif                                // trajectory kinds / MCLMC — the same functor inside LrWrap / KinWrap, as for the built-in densities
+
+// Optional: a density that defines expanded_dim / expand_element (nuts_kernels.hpp has_expand; include/nuts_amd.h "User densities") exports
+// its expansion pass, nm_module_expand (the launch of nm_expand_kernel<density>, nuts_expand.hpp) and nm_module_expanded_dim (host).  A
+// density without the members exports neither symbol — the engine looks them up by name and takes the identity when they are absent —
+// which is why the two are members of a class template that is specialised on the trait and given their C names, not plain functions.
+namespace nm {
+template <class D, bool = has_expand<D>::value> struct ModuleExpand {};
+template <class D> struct ModuleExpand<D, true> {
+    static int launch(const double* d_params, uint64_t dim, uint64_t edim, uint64_t n_rows, const double* d_positions, double* d_expanded,
+                      unsigned grid_cap, void* stream) __asm__("nm_module_expand");
+    static uint64_t expanded_dim(uint64_t dim, const double* h_params, uint64_t n_params) __asm__("nm_module_expanded_dim");
+};
+template <class D>
+int ModuleExpand<D, true>::launch(const double* d_params, uint64_t dim, uint64_t edim, uint64_t n_rows, const double* d_positions, double* d_expanded,
+                                  unsigned grid_cap, void* stream) {
+    return (int)launch_expand_t<D>(d_params, dim, edim, n_rows, d_positions, d_expanded, grid_cap, static_cast<hipStream_t>(stream));
+}
+template <class D>
+uint64_t ModuleExpand<D, true>::expanded_dim(uint64_t dim, const double* h_params, uint64_t n_params) { return D::expanded_dim(dim, h_params, n_params); }
+template struct ModuleExpand<NM_MODULE_DENSITY>;
+}  // namespace nm
 
 extern "C" {
 // {sizeof(KParams), NM_ABI_VERSION, DPL, W, lanes per chain of the group form or 0, 1 if built for chains wider than one block,

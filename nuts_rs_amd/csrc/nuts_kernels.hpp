@@ -315,6 +315,20 @@ NM_DEV void buf_store2(rsrc_t r, int voff, int soff, double a, double b) {
 // densities: eval(x, gx, dim) -> logp (wave-uniform), fills gx; padded elements (index >= dim) must give
 // zero terms and zero gradient.
 // ---------------------------------------------------------------------------------------------
+// `CpuLogpFunc::expand_vector` (reference src/math/cpu_math.rs:892-899): what the user reads instead of the unconstrained point.  OPTIONAL — a
+// density that defines neither member expands to the position itself, as every density the reference ships does (src/math/test_logps.rs:60-66):
+//   static NM_HD uint64_t expanded_dim(uint64_t dim, const double* params, uint64_t n_params)          length of the expanded vector (host and device)
+//   static NM_DEV double expand_element(const double* params, int dim, const double* x, int j)         element j of the expansion of x[0 .. dim)
+// Written per output element: the result is a function of (params, x, j) alone, whatever the mapping of threads to rows (nuts_expand.hpp:
+// the lanes of a wavefront hold different rows and elements; x may point to LDS or to global memory).  Special functions there are the
+// per-lane, always-inlined xexp / xlog / xlog1p — the same operation sequence, so the same bits, as dexp / dlog / dlog1p; the wave-uniform
+// uexp / ulog of `eval` would hand every lane the first lane's value.  No random stream: an expansion is deterministic.
+NM_DEV double xexp(double x) { return dexp_impl<false>(x); }
+NM_DEV double xlog(double x) { return dlog_impl<false>(x); }
+NM_DEV double xlog1p(double x) { return dlog1p_impl<false>(x); }
+template <class D, class = void> struct has_expand { static constexpr bool value = false; };
+template <class D> struct has_expand<D, std::void_t<decltype(&D::expanded_dim), decltype(&D::expand_element)>> { static constexpr bool value = true; };
+
 struct IidNormal {
     static constexpr bool kNeedsLdsVector = false;
     // element form of eval (leapfrog's fused loop): gradient element and, through `term`, what eval adds to its sum for this element
@@ -550,6 +564,15 @@ struct EightSchools {
         }
         (void)dim;
         return R.sum(acc);
+    }
+    // what the user reads (has_expand above): (mu, log tau, theta~[8]) -> (mu, tau, theta[8]), theta_i = mu + tau theta~_i as eval forms it
+    static NM_HD uint64_t expanded_dim(uint64_t, const double*, uint64_t) { return 10; }
+    static NM_DEV double expand_element(const double*, int, const double* x, int j) {
+        if (j == 0) return x[0];
+        const double tau = xexp(x[1]);
+        if (j == 1) return tau;
+        const double scaled = tau * x[j];
+        return x[0] + scaled;
     }
 };
 

@@ -280,6 +280,14 @@ class LogpSpec:
         spec.host_threads = threads
         return spec
 
+    def expanded_dim(self):
+        """Length of this density's expanded vector (`CpuLogpFunc::expand_vector`, src/math/cpu_math.rs:892-899): `dim` for the densities
+        that expand to the position itself, 10 for the 8 schools (mu, tau, theta[8]), a module's own answer.  Host only, no GPU."""
+        c = self.to_c()
+        out = C.c_uint64()
+        check(_lib.load().nm_logp_expanded_dim(C.byref(c), C.byref(out)))
+        return int(out.value)
+
     def to_c(self):
         self._keep = np.ascontiguousarray(self.params, dtype=np.float64)
         path = self.module_path.encode() if self.module_path else None
@@ -335,6 +343,10 @@ class ChainBatch:
 
     def dim(self):
         return self.logp.dim
+
+    def expanded_dim(self):
+        """Length of an expanded draw (nm_engine_expanded_dim)."""
+        return int(_lib.load().nm_engine_expanded_dim(self._h))
 
     def threads_per_chain(self):
         """64 x waves cooperating on a chain; fixes the reduction order over dim (oracle: gpu_cfg(threads_per_chain))."""
@@ -448,10 +460,11 @@ class ChainBatch:
             names += ["divergence_start", "divergence_start_gradient", "divergence_end"]
         return names
 
-    def expanded_draw_many(self, n_draws, vectors=None):
+    def expanded_draw_many(self, n_draws, vectors=None, expanded=False):
         """`Chain::expanded_draw` x n_draws (src/chain.rs:190-204): positions, scalar stats and a dict of the
         vector-valued statistics ([n_draws, n_chains, dim]; rows of events that did not happen are NaN).
-        `vectors` defaults to what the settings' store_* switches select."""
+        `vectors` defaults to what the settings' store_* switches select.  expanded=True: a fourth array
+        [n_draws, n_chains, expanded_dim()], the density's expand_vector of every draw, computed on the device."""
         names = list(self.stored_vectors() if vectors is None else vectors)
         bad = [k for k in names if k not in VECTOR_STATS]
         if bad:
@@ -464,8 +477,11 @@ class ChainBatch:
         out.d_positions, out.d_stats = pos.ctypes.data, st.ctypes.data
         for k, a in vec.items():
             setattr(out, "d_" + k, a.ctypes.data)
+        if expanded:
+            ex = np.empty(shape[:2] + (self.expanded_dim(),))
+            out.d_expanded = ex.ctypes.data
         check(_lib.load().nm_engine_draw_ex_to_host(self._h, n_draws, C.byref(out)))
-        return pos, st, vec
+        return (pos, st, vec, ex) if expanded else (pos, st, vec)
 
     def draw_device(self, n_draws, d_positions=0, d_stats=0, sync=True):
         """n_draws draws with results left in caller-provided device buffers (raw pointers, e.g. tensor.data_ptr())."""
@@ -473,11 +489,12 @@ class ChainBatch:
         fn = L.nm_engine_draw if sync else L.nm_engine_draw_async
         check(fn(self._h, n_draws, C.c_void_p(d_positions or None), C.c_void_p(d_stats or None)))
 
-    def draw_device_ex(self, n_draws, positions=0, stats=0, **vectors):
+    def draw_device_ex(self, n_draws, positions=0, stats=0, expanded=0, **vectors):
         """`expanded_draw` x n_draws with every result left in caller-provided DEVICE buffers (raw pointers): positions,
-        stats and any of VECTOR_STATS by name (e.g. gradient=tensor.data_ptr())."""
+        stats, any of VECTOR_STATS by name (e.g. gradient=tensor.data_ptr()) and `expanded` ([n_draws, n_chains, expanded_dim()];
+        needs positions)."""
         out = NmDrawOutputs()
-        out.d_positions, out.d_stats = positions or None, stats or None
+        out.d_positions, out.d_stats, out.d_expanded = positions or None, stats or None, expanded or None
         for k, ptr in vectors.items():
             if k not in VECTOR_STATS:
                 raise ValueError(f"unknown vector statistic {k}")
@@ -486,6 +503,25 @@ class ChainBatch:
 
     def synchronize(self):
         check(_lib.load().nm_engine_synchronize(self._h))
+
+    def expand(self, positions):
+        """The density's expand_vector of rows the caller already holds (nm_engine_expand): positions [..., dim] -> [..., expanded_dim()].
+        A float64 torch tensor on the engine's device is expanded in place where it lies and a tensor is returned; anything else goes
+        through numpy and a device round trip."""
+        import torch
+        is_tensor = isinstance(positions, torch.Tensor)
+        t = positions if is_tensor else torch.from_numpy(np.ascontiguousarray(positions, dtype=np.float64))
+        if t.dtype != torch.float64 or t.dim() < 1 or t.shape[-1] != self.logp.dim:
+            raise ValueError(f"positions must be float64 [..., {self.logp.dim}]")
+        t = t.contiguous()
+        if not t.is_cuda:
+            t = t.cuda()
+        n_rows = int(np.prod(t.shape[:-1], dtype=np.int64))
+        out = torch.empty(tuple(t.shape[:-1]) + (self.expanded_dim(),), dtype=torch.float64, device=t.device)
+        torch.cuda.current_stream(t.device).synchronize()       # the engine launches on its own stream: the rows must be there
+        check(_lib.load().nm_engine_expand(self._h, n_rows, C.c_void_p(t.data_ptr() or None), C.c_void_p(out.data_ptr() or None)))
+        self.synchronize()
+        return out if is_tensor else out.cpu().numpy()
 
     # ---- the low-rank transformation (LowRankNutsSettings; reference src/transform/low_rank.rs) ----
     def set_transform(self, stds, mean, vals, vecs, mu_low_rank):
@@ -566,10 +602,11 @@ class ChainBatch:
         return _lib.load().nm_engine_stream(self._h)
 
 
-def sample(settings: DiagNutsSettings, logp: LogpSpec, x0=None, chain_id_offset=0, device=-1, chunk_bytes=0):
+def sample(settings: DiagNutsSettings, logp: LogpSpec, x0=None, chain_id_offset=0, device=-1, chunk_bytes=0, expanded=False):
     """The reference's `Sampler` loop for every chain (src/sampler.rs:1120-1199): init, num_tune + num_draws draws.
 
-    Returns (positions [num_tune+num_draws, n_chains, dim], stats)."""
+    Returns (positions [num_tune+num_draws, n_chains, dim], stats), and with expanded=True a third array, the expanded trace
+    [num_tune+num_draws, n_chains, expanded dim] (the density's expand_vector of every draw)."""
     batch = ChainBatch(settings, logp, settings.num_chains, chain_id_offset, device)
     batch.init_with_retries(x0)                      # up to 500 initial points per chain, like the reference
     total = settings.num_tune + settings.num_draws
@@ -577,14 +614,20 @@ def sample(settings: DiagNutsSettings, logp: LogpSpec, x0=None, chain_id_offset=
     # chunk's kernel); `chunk_bytes` > 0 additionally bounds the draws per call (e.g. to poll for interrupts in between)
     pos = np.empty((total, batch.n_chains, logp.dim))
     st = np.zeros((total, batch.n_chains), dtype=STATS_DTYPE)
-    per_draw = batch.n_chains * (logp.dim * 8 + STATS_DTYPE.itemsize)
+    ex = np.empty((total, batch.n_chains, batch.expanded_dim())) if expanded else None
+    per_draw = batch.n_chains * (logp.dim * 8 + STATS_DTYPE.itemsize + (ex.shape[2] * 8 if expanded else 0))
     chunk = max(1, min(total, chunk_bytes // per_draw)) if chunk_bytes else total
     done = 0
     try:
         while done < total:
             n = min(chunk, total - done)
-            batch.draw_many(n, out=(pos[done:done + n], st[done:done + n]))
+            if expanded:
+                o = NmDrawOutputs()
+                o.d_positions, o.d_stats, o.d_expanded = pos[done:].ctypes.data, st[done:].ctypes.data, ex[done:].ctypes.data
+                check(_lib.load().nm_engine_draw_ex_to_host(batch._h, n, C.byref(o)))
+            else:
+                batch.draw_many(n, out=(pos[done:done + n], st[done:done + n]))
             done += n
     finally:
         batch.close()
-    return pos, st
+    return (pos, st, ex) if expanded else (pos, st)
