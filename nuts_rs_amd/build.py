@@ -30,7 +30,7 @@ UNITS = ["kern_tile_mvn_prec.hip", "kern_tile_mvn_diag.hip", "kern_lockstep.hip"
 # (kern_expand.hip, the expansion pass: nuts_expand.hpp).
 VARIANT_FLAGS = {"": [], "small": ["-DNM_TU_PART=1", "-DNM_DETMATH_INLINE=1"], "large": ["-DNM_TU_PART=2"], "inl": ["-DNM_DETMATH_INLINE=1"]}
 NO_CALL_VARIANTS = ("small", "inl")
-HEADERS = ["nuts_kernels.hpp", "nuts_launch.hpp", "dev_math.hpp", "detmath_tables.hpp", "zig_tables.hpp", "nuts_group.hpp", "nuts_group_impl.hpp", "nuts_tile.hpp", "nuts_expand.hpp", os.path.join("..", "..", "include", "nuts_amd.h")]
+HEADERS = ["nuts_kernels.hpp", "nuts_adapt.hpp", "nuts_launch.hpp", "dev_math.hpp", "detmath_tables.hpp", "zig_tables.hpp", "nuts_group.hpp", "nuts_group_impl.hpp", "nuts_tile.hpp", "nuts_expand.hpp", os.path.join("..", "..", "include", "nuts_amd.h")]
 # -ffp-contract=off: FMAs only where the reference writes mul_add
 # -Wno-pass-failed: "loop not unrolled" remarks of the matrix-core kernel's partially unrolled product loops (a diagnostic only)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-pass-failed"]

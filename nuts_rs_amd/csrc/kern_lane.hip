@@ -32,7 +32,7 @@ hipError_t launch_lane_d(int query, bool tune, const KParams& P, const lane::Lan
     return hipErrorInvalidValue;
 }
 }  // namespace
-// query = 1: *occ = resident blocks (wavefronts) per CU; 2: launch the kernel with unsynchronised draws; 0: the synchronised one
+// query = 1: *occ = resident blocks (wavefronts) per CU; 0: launch the kernel
 hipError_t launch_lane(uint64_t logp_kind, int query, bool tune, const KParams& P, const lane::LaneParams& LP, unsigned grid, hipStream_t stream, int* occ) {
     switch (logp_kind) {
     case NM_LOGP_IID_NORMAL: return launch_lane_d<IidNormal>(query, tune, P, LP, grid, stream, occ);

@@ -1452,6 +1452,10 @@ NM_DEV double powi_rs(double a, int32_t b) {
     return b < 0 ? 1.0 / mul : mul;
 }
 
+}  // namespace nm
+#include "nuts_adapt.hpp"     // the chain's scalar step-size protocol as the one-chain-per-lane and lockstep kernels share it
+namespace nm {
+
 // Hamiltonian::init_state at x with the current mass matrix (reference transformed_hamiltonian.rs:640-661,
 // check_all :310-324).  Fills st.z, st.g, gx, st.logp; returns false for BadInitGrad.
 template <int DPL, int W, class Dens>

@@ -27,7 +27,7 @@
 // own order is its SIMD width's).  Every elementwise operation is the one-chain kernel's.
 #pragma once
 #include "nuts_tile.hpp"     // tile mode, TileMats, taddr, v4d; nuts_kernels.hpp
-#include "nuts_lane.hpp"     // the per-lane scalar toolkit: lexp / llog / llogaddexp, LRng, LAccept
+#include "nuts_lane.hpp"     // the per-lane scalar toolkit: lexp / llogaddexp, LMath, LRng, LAccept
 
 namespace nm {
 namespace lock {
@@ -36,7 +36,7 @@ using tile::TileMats;
 using tile::taddr;
 using tile::v4d;
 using lane::lexp;
-using lane::llog;
+using lane::LMath;
 using lane::llogaddexp;
 using lane::LRng;
 using lane::LAccept;
@@ -519,68 +519,23 @@ struct Logic {
         doubling_begin();
     }
 
-    NM_DEV void update_estimator(bool late) {                     // DualAverage::advance / Adam::advance (nuts_lane.hpp l_update_estimator)
-        const nm_settings& s = P.s;
-        if (s.step_size_method == NM_STEP_FIXED) return;
-        const double accept_stat = late ? sc.last_sym_mean_tree_accept : sc.last_mean_tree_accept;
-        if (s.step_size_method == NM_STEP_ADAM) {
-            const double gradient = accept_stat - s.target_accept;
-            sc.adam_t += 1;
-            sc.adam_m = s.adam_beta1 * sc.adam_m + (1.0 - s.adam_beta1) * gradient;
-            sc.adam_v = s.adam_beta2 * sc.adam_v + (1.0 - s.adam_beta2) * gradient * gradient;
-            const double m_hat = sc.adam_m / (1.0 - powi_rs(s.adam_beta1, (int32_t)sc.adam_t));
-            const double v_hat = sc.adam_v / (1.0 - powi_rs(s.adam_beta2, (int32_t)sc.adam_t));
-            sc.log_step += s.adam_learning_rate * m_hat / (__builtin_sqrt(v_hat) + s.adam_epsilon);
-            return;
-        }
-        const double w = 1. / ((double)sc.da_count + s.da_t0);
-        sc.hbar = (1. - w) * sc.hbar + w * (s.target_accept - accept_stat);
-        sc.log_step = sc.mu - sc.hbar * __builtin_sqrt((double)sc.da_count) / s.da_gamma;
-        sc.log_step = fmin_rs(sc.log_step, P.ln_max_step);
-        const double mk = lexp(-s.da_k * llog((double)sc.da_count));
-        sc.log_step_adapted = mk * sc.log_step + (1. - mk) * sc.log_step_adapted;
-        sc.da_count += 1;
-    }
-    NM_DEV void update_stepsize(bool use_best_guess) {
-        const nm_settings& s = P.s;
-        const double step = s.step_size_method == NM_STEP_FIXED ? s.fixed_step_size
-                          : s.step_size_method == NM_STEP_ADAM ? lexp(sc.log_step)
-                          : (use_best_guess ? lexp(sc.log_step_adapted) : lexp(sc.log_step));
-        if (s.has_jitter) {
-            const double v12 = u2d((rng.next_u64() >> 12) | 0x3ff0000000000000ull);
-            const double j = (v12 - 1.0) * P.jitter_scale + P.jitter_low;
-            sc.step_size = step * j;
-        } else {
-            sc.step_size = step;
-        }
-    }
     // GlobalStrategy::adapt with a FROZEN transformation (adapt_lr of nuts_kernels.hpp with frozen = true): the schedule's
     // is_late, the step-size estimator and the new step size
     NM_DEV void adapt_frozen() {
         const nm_settings& s = P.s;
         const uint64_t draw = sc.draw_count;
-        sc.last_mean_tree_accept = K.col.mean();
-        sc.last_sym_mean_tree_accept = K.col.mean_sym();
-        sc.last_n_steps = K.col.count;
-        sc.last_max_energy_error = K.col.max_energy_error;
-        if (draw >= s.num_tune) { update_stepsize(true); sc.tuning = 0; return; }
+        record_collector(sc, K.col);
+        if (draw >= s.num_tune) { update_stepsize<LMath>(sc, P, rng, true); sc.tuning = 0; return; }
         if (draw < P.final_step_size_window) {
             const bool is_early = draw < P.early_end;
-            uint64_t next_window_size;
-            if (is_early) next_window_size = s.early_mass_matrix_switch_freq;
-            else {
-                const double gv = (double)sc.current_window_size * s.mass_matrix_window_growth;
-                const double fl = __builtin_floor(gv);
-                const uint64_t grown = (uint64_t)((gv - fl >= 0.5) ? fl + 1.0 : fl);
-                next_window_size = sc.current_window_size + 1 > grown ? sc.current_window_size + 1 : grown;
-            }
-            const bool is_late = next_window_size + draw > P.final_step_size_window;
-            update_estimator(is_late);
-            update_stepsize(false);
+            const uint64_t next_window = next_window_size(sc, s, is_early);
+            const bool is_late = next_window + draw > P.final_step_size_window;
+            update_estimator<LMath>(sc, P, is_late);
+            update_stepsize<LMath>(sc, P, rng, false);
             return;
         }
-        update_estimator(true);
-        update_stepsize(draw == s.num_tune - 1);
+        update_estimator<LMath>(sc, P, true);
+        update_stepsize<LMath>(sc, P, rng, draw == s.num_tune - 1);
     }
 
     // the chosen point is in the stripes' registers (x, g_x, z, g_z), sum (z + g_z)^2 in sums[0]: statistics, adaptation, next draw
@@ -603,8 +558,7 @@ struct Logic {
         adapt_frozen();
         out.tuning = sc.tuning; out.n_steps = sc.last_n_steps;
         out.step_size = sc.step_size;
-        out.step_size_bar = P.s.step_size_method == NM_STEP_FIXED ? P.s.fixed_step_size
-                          : P.s.step_size_method == NM_STEP_ADAM ? lexp(sc.log_step) : lexp(sc.log_step_adapted);
+        out.step_size_bar = step_size_bar<LMath>(sc, P.s);
         out.mean_tree_accept = sc.last_mean_tree_accept; out.mean_tree_accept_sym = sc.last_sym_mean_tree_accept;
         out.max_energy_error = sc.last_max_energy_error;
         out.chain_status = NM_CHAIN_OK;

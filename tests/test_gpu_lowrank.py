@@ -18,31 +18,9 @@ import pytest
 
 import nuts_rs_amd as N
 from nuts_rs_amd import _lib
-from helpers import assert_bit_exact, oracle_settings
+from helpers import assert_bit_exact, correlated_precision, estimator_pair, oracle_settings, random_transform, run_fixed  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-def random_transform(rng, dim, rank, per_chain=0):
-    shape = (per_chain,) if per_chain else ()
-    stds = np.exp(rng.normal(0, 0.5, shape + (dim,)))
-    mean = rng.normal(0, 1, shape + (dim,))
-    mu = rng.normal(0, 0.3, shape + (dim,))
-    vals = np.exp(rng.uniform(-2, 3, shape + (rank,)))
-    if per_chain:
-        vecs = np.stack([np.linalg.qr(rng.normal(size=(dim, rank)))[0].T for _ in range(per_chain)])
-    else:
-        vecs = np.linalg.qr(rng.normal(size=(dim, rank)))[0].T
-    return stds, mean, vals, np.ascontiguousarray(vecs), mu
-
-
-def correlated_precision(rng, dim, rank, scale=50.0):
-    u = np.linalg.qr(rng.normal(size=(dim, rank)))[0]
-    sigma = np.eye(dim) + u @ np.diag(rng.uniform(5.0, scale, rank)) @ u.T
-    sc = np.exp(rng.normal(0, 0.5, dim))
-    sigma = np.diag(sc) @ sigma @ np.diag(sc)
-    prec = np.linalg.inv(sigma)
-    return (prec + prec.T) / 2, sigma
 
 
 @pytest.mark.parametrize("dim,rank", [(3, 1), (10, 4), (40, 40), (100, 7), (256, 16), (256, 256), (1000, 5)])
@@ -67,28 +45,6 @@ def test_lowrank_maps_bit_exact(oracle, dim, rank):
 
 def lowrank_settings(**kw):
     return N.LowRankNutsSettings(**kw)
-
-
-def run_fixed(oracle, logp, settings, n_chains, transform, n_draws, waves_per_chain=0, dims_per_lane=0, chain_tiles=0,
-              expect_tiles=None, splits=()):
-    x0 = oracle.init_positions_uniform(settings.seed, 0, n_chains, logp.dim)
-    b = N.ChainBatch(settings, logp, n_chains, waves_per_chain=waves_per_chain, dims_per_lane=dims_per_lane, chain_tiles=chain_tiles)
-    assert (b.set_position(x0) == 0).all()
-    b.set_transform(*transform)
-    cuts = [0] + [c for c in splits if 0 < c < n_draws] + [n_draws]
-    parts = [b.draw_many(hi - lo) for lo, hi in zip(cuts[:-1], cuts[1:])]
-    pos, st = np.concatenate([p for p, _ in parts]), np.concatenate([q for _, q in parts])
-    tpc = b.threads_per_chain()
-    tiles = b.tile_launches() > 0              # the matrix-core kernels sum U'v sequentially: the oracle's lr_seq_dots mode
-    order = b.reduce_order()                   # (1: the tile kernel, 2: the lockstep kernel with its own order of the sums over dim)
-    if expect_tiles is not None:
-        assert tiles == expect_tiles
-    assert (order > 0) == tiles and (order == 2) == (b.lockstep_launches() > 0)
-    b.close()
-    pos_o, st_o, _, failed = oracle.run(oracle_settings(oracle, settings), logp.kind, logp.dim, logp.params,
-                                        oracle.gpu_cfg(tpc, lr_seq_dots=order), n_chains, x0, n_draws, n_threads=8, transform=transform)
-    assert failed == 0
-    return pos, st, pos_o, st_o
 
 
 @pytest.mark.parametrize("case", ["dim10_rank3_shared", "dim100_rank6_per_chain", "dim40_full_rank", "dim300_rank12_two_waves",
@@ -139,15 +95,6 @@ def test_matrix_core_kernel_bit_exact(oracle, dim, rank, n_chains, chain_tiles):
     pos, st, pos_o, st_o = run_fixed(oracle, N.LogpSpec.mvn_precision(prec), s, n_chains, tr, 60, expect_tiles=True, splits=(1, 33), chain_tiles=chain_tiles)
     assert_bit_exact(pos, st, pos_o, st_o)
     assert len(np.unique(st["depth"])) >= 2                       # trees of different sizes inside a tile
-
-
-def estimator_pair(oracle):
-    """the oracle's LAPACK estimator, as a callback for the oracle and as a callback for the engine (same function)"""
-    from oracle import lowrank as LR
-    rec = []
-    cb_o = LR.estimator_callback(rec)
-    cb_e = C.cast(cb_o, _lib.LOWRANK_ESTIMATOR_FN)
-    return cb_o, cb_e, rec
 
 
 @pytest.mark.parametrize("case", ["diag_normal_dim12", "mvn_dim20_correlated", "funnel_dim11", "mvn_dim64_update_freq5"])
