@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define NM_ABI_VERSION 17
+#define NM_ABI_VERSION 18
 
 typedef enum nm_status {
     NM_OK = 0,
@@ -683,6 +683,72 @@ nm_status nm_pooled_partials(uint64_t n_rows, uint64_t dim, const double* d_posi
 nm_status nm_pooled_exchange(void* rccl_comm, uint64_t world, uint64_t dim, const double* d_payload, double* d_gathered, void* stream);
 nm_status nm_pooled_finish(uint64_t world, uint64_t dim, const double* d_gathered, double* d_sigma, double* d_mean, double* d_count, void* stream);
 const char* nm_pooled_last_error(void);
+
+/* ---------------------------------------------------------------------------------------------
+ * Posterior summaries of a recorded trace, computed where the trace lies: per element the mean, the standard deviation, the
+ * within-series variance, split R-hat, the effective sample size and the chain-averaged autocorrelations.  NO reference
+ * counterpart (nutpie leaves this to ArviZ on the host): like the pooled adaptation it is defined by THIS repository; the
+ * formulas are the Stan / ArviZ ones (split R-hat, Geyer's initial monotone sequence) WITHOUT rank-normalisation.  Engine-free.
+ *
+ * Input: d_draws[n_draws][n_chains][dim], f64, row-major, as nm_engine_draw_ex leaves d_positions or d_expanded.  h_chain_ids
+ * (host, strictly increasing, < n_chains) selects C' = n_chain_ids chains; NULL = all chains (C' = n_chains).  N = n_draws.
+ *   split = 1: n = N / 2 (rounded down), M = 2 C'; series m < C' is draws 0 .. n-1 of selected chain m, series m >= C' is draws
+ *              N-n .. N-1 of selected chain m - C' (the middle draw of an odd N belongs to neither half);
+ *   split = 0: n = N, M = C'.          L = min(max_lag, n - 1).
+ * Per series m and element d — every sum serial in t ascending, every operation ONE binary64 + - * or / (no fused multiply-add):
+ *   mean_m = (sum_t x_t) / n;   y_t = x_t - mean_m;   acov_m[k] = (sum_{t=k}^{n-1} y_t * y_{t-k}) / n, k = 0 .. L;
+ *   var_m = acov_m[0] * n / (n - 1).
+ * Across series, per d (and per k): series are summed in chunks of NM_SUMMARY_CHUNK_CHAINS consecutive series, inside a chunk
+ * serially in m from 0.0, the chunk partials then in chunk order from 0.0 (the pattern of nm_pooled_partials: the bits do not
+ * depend on the grid, the block size or on what else runs on the device):
+ *   gm = sum(mean_m) / M;   W = sum(var_m) / M;   Bn = sum((mean_m - gm)^2) / (M - 1);   var_plus = W * (n - 1) / n + Bn;
+ *   sd = sqrt(var_plus);   rhat = sqrt(var_plus / W);   acov[k] = sum(acov_m[k]) / M;
+ *   rho[k] = 1 - (W - acov[k]) / var_plus, rho[0] = 1 exactly.
+ * ESS (Geyer's initial monotone sequence on rho): P_T = rho[2T] + rho[2T+1]; tau = -1 + 2 P_0; prev = P_0; for T = 1, 2, ... while
+ * 2T + 1 <= L: stop at the first P_T that is not > 0, else P = min(P_T, prev), prev = P, tau += 2 P.   ess = (M * n) / tau.
+ * ess_truncated = 1 when the loop ran out of lags without meeting a non-positive pair: the reported ESS is then an over-estimate
+ * (the caller asked for too few lags).  There is no log10 cap on the ESS.  A constant column gives the NaN that IEEE arithmetic
+ * gives (0 / 0 in rhat and rho).  Rank-normalisation, nested R-hat and quantiles are OUT OF SCOPE.
+ *
+ * Outputs: device pointers, any may be NULL.  d_mean = gm, d_within_var = W, d_autocorr = rho [L+1][dim], d_chain_mean /
+ * d_chain_var = mean_m / var_m [M][dim].  Asynchronous on `stream` when h_chain_ids is NULL; WITH chain ids the call uploads them and
+ * waits for `stream` (hipStreamSynchronize) before it returns, so that the host array is free on return — it then blocks, and cannot
+ * be issued on a stream that is being captured.  The trace is read twice; scratch (stream-ordered, freed
+ * behind the kernels) is chunks x (L + 4) x dim doubles plus, when d_chain_mean is NULL, the M x dim series means.
+ * NM_ERR_INVALID_ARG — decided before any device call — for: a null spec / draws / outputs; dim, n_chains or n_draws == 0;
+ * max_lag outside 1 .. 64; n < 2; M < 2; chain ids not strictly increasing or out of range (n_chain_ids == 0 with ids given).
+ * Two size limits of the launch grids are refused the same way: M above 65535 * NM_SUMMARY_CHUNK_CHAINS (2097120) series, and dim
+ * above 128 * (2^31 - 1).
+ * h_chain_ids and d_ess_truncated are declared void* although they point to uint64_t (the first only read): the binding check of
+ * this repository (tests/test_integration_binding.py) parses every struct of this header and knows a closed set of field types, to
+ * which `const uint64_t*` and `uint64_t*` do not belong.  The C++ wrapper (nuts_amd.hpp) takes a typed `const std::vector<uint64_t>*`.
+ * nm_summary_last_error: the message of this call's last failure on the calling thread.
+ * ------------------------------------------------------------------------------------------- */
+#define NM_SUMMARY_CHUNK_CHAINS 32
+typedef struct nm_summary_spec {
+    uint64_t n_draws;
+    uint64_t n_chains;
+    uint64_t dim;
+    uint64_t split;                /* 0 / 1 */
+    uint64_t max_lag;              /* 1 .. 64 */
+    uint64_t n_chain_ids;          /* ignored when h_chain_ids is NULL */
+    void* h_chain_ids;             /* const uint64_t[n_chain_ids] on the host, only read; NULL = all chains */
+    uint64_t reserved[2];
+} nm_summary_spec;
+typedef struct nm_summary_outputs {          /* device pointers, any may be NULL */
+    double* d_mean;          /* [dim] */
+    double* d_sd;            /* [dim] */
+    double* d_within_var;    /* [dim] */
+    double* d_rhat;          /* [dim] */
+    double* d_ess;           /* [dim] */
+    void* d_ess_truncated;   /* uint64_t[dim] */
+    double* d_autocorr;      /* [L+1][dim], the rho above */
+    double* d_chain_mean;    /* [M][dim] */
+    double* d_chain_var;     /* [M][dim] */
+    uint64_t reserved[3];
+} nm_summary_outputs;
+nm_status nm_summarize_draws(const nm_summary_spec* spec, const double* d_draws, const nm_summary_outputs* out, void* stream);
+const char* nm_summary_last_error(void);
 
 const char* nm_last_error(void);
 uint64_t    nm_abi_version(void);

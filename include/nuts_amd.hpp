@@ -317,6 +317,17 @@ private:
     nm_engine* h_ = nullptr;
 };
 
+// Posterior summaries of a trace that lies on the device (nm_summarize_draws; no reference counterpart, defined in nuts_amd.h).
+// d_draws is [n_draws][n_chains][dim]; every pointer of `out` is a device pointer or null; asynchronous on `stream`.
+inline void summarize_draws(const double* d_draws, uint64_t n_draws, uint64_t n_chains, uint64_t dim, const nm_summary_outputs& out,
+                            bool split = true, uint64_t max_lag = 32, const std::vector<uint64_t>* chain_ids = nullptr, void* stream = nullptr) {
+    nm_summary_spec spec{};
+    spec.n_draws = n_draws; spec.n_chains = n_chains; spec.dim = dim; spec.split = split ? 1 : 0; spec.max_lag = max_lag;
+    if (chain_ids) { spec.n_chain_ids = chain_ids->size(); spec.h_chain_ids = const_cast<uint64_t*>(chain_ids->data()); }
+    const nm_status st = nm_summarize_draws(&spec, d_draws, &out, stream);
+    if (st != NM_OK) throw NutsError(st, nm_summary_last_error());
+}
+
 struct ChainProgress {             // src/sampler.rs:1009-1051
     uint64_t finished_draws = 0, total_draws = 0, divergences = 0;
     bool tuning = true, started = false;

@@ -11,14 +11,15 @@ All arithmetic happens in libnuts_amd.so (HIP); this file only marshals argument
 """
 import ctypes as C
 import os
+import sys
 from dataclasses import dataclass, field, fields
 from typing import Optional
 
 import numpy as np
 
 from . import _lib
-from ._lib import (NmDrawOutputs, NmEngineConfig, NmLogpSpec, NmSettings, NutsAmdError, STATS_DTYPE, VECTOR_STATS,
-                   check)
+from ._lib import (NmDrawOutputs, NmEngineConfig, NmLogpSpec, NmSettings, NmSummaryOutputs, NmSummarySpec, NutsAmdError, STATS_DTYPE,
+                   SUMMARY_OUTPUTS, VECTOR_STATS, check)
 
 LOGP_IID_NORMAL, LOGP_DIAG_NORMAL, LOGP_FUNNEL, LOGP_EIGHT_SCHOOLS, LOGP_MVN_PREC, LOGP_MODULE, LOGP_HOST_CALLBACK = 0, 1, 2, 3, 4, 5, 6
 STEP_DUAL_AVERAGE, STEP_ADAM, STEP_FIXED = 0, 1, 2
@@ -308,6 +309,10 @@ class ChainBatch:
         self.logp = logp
         self.n_chains = int(n_chains if n_chains is not None else settings.num_chains)
         self.chain_id_offset = chain_id_offset
+        # the GPU the engine lives on, for buffers this class allocates itself (draw_summary): `device`, or for -1 the current one
+        # — torch's when torch has initialised it (one HIP runtime per process, _lib._preload_torch_hip_runtime), else 0
+        torch = sys.modules.get("torch")
+        self._device = int(device) if device >= 0 else (torch.cuda.current_device() if torch is not None and torch.cuda.is_initialized() else 0)
         L = _lib.load()
         cfg = NmEngineConfig()
         L.nm_engine_config_default(C.byref(cfg))
@@ -523,6 +528,29 @@ class ChainBatch:
         self.synchronize()
         return out if is_tensor else out.cpu().numpy()
 
+    def draw_summary(self, n_draws, expanded=False, split=True, max_lag=32):
+        """n_draws draws of every chain into device buffers, summarised where they lie (summarize_draws): returns (Summary, stats
+        [n_draws, n_chains] on the host).  Chains whose last chain_status is not NM_CHAIN_OK are left out of the summary.
+        expanded=True summarises the expanded draws instead of the positions.  No position row crosses PCIe."""
+        import torch
+        dev = torch.device("cuda", self._device)                # the engine's device, whatever torch's current one is
+        pos = torch.empty((n_draws, self.n_chains, self.logp.dim), dtype=torch.float64, device=dev)
+        # (the engine never writes the rows of a chain that has stopped or never started: all-ones rows are the ones it left out)
+        st = torch.full((n_draws, self.n_chains, STATS_DTYPE.itemsize), 0xFF, dtype=torch.uint8, device=dev)
+        ex = torch.empty((n_draws, self.n_chains, self.expanded_dim()), dtype=torch.float64, device=dev) if expanded else None
+        torch.cuda.current_stream(dev).synchronize()            # the engine launches on its own stream
+        try:
+            self.draw_device_ex(n_draws, positions=pos.data_ptr(), stats=st.data_ptr(), expanded=ex.data_ptr() if expanded else 0)
+        except NutsAmdError as e:
+            if e.status != _lib.NM_ERR_LOGP_FAILURE:             # (stopped chains: the healthy ones' rows are there)
+                raise
+        self.synchronize()
+        stats = st.cpu().numpy().view(STATS_DTYPE).reshape(n_draws, self.n_chains)
+        good = np.flatnonzero(stats["chain_status"][-1] == 0)
+        stats[stats["chain_status"] == np.uint64(2**64 - 1)] = np.zeros((), dtype=STATS_DTYPE)       # unwritten rows read as in draw_many
+        ids = None if len(good) == self.n_chains else good
+        return summarize_draws(ex if expanded else pos, split=split, max_lag=max_lag, chain_ids=ids), stats
+
     # ---- the low-rank transformation (LowRankNutsSettings; reference src/transform/low_rank.rs) ----
     def set_transform(self, stds, mean, vals, vecs, mu_low_rank):
         """`LowRankMassMatrix::update(stds, mean, vals, vecs, mean_low_rank)` for every chain.  vecs: [n_eig, dim] (one
@@ -600,6 +628,57 @@ class ChainBatch:
 
     def stream(self):
         return _lib.load().nm_engine_stream(self._h)
+
+
+@dataclass
+class Summary:
+    """Posterior summaries of a trace (nm_summarize_draws; defined by this repository, include/nuts_amd.h): arrays over the elements of
+    a draw — autocorr is [L + 1, dim], chain_mean / chain_var are [n_series, dim] (the halves of the chains when split)."""
+    mean: np.ndarray
+    sd: np.ndarray
+    within_var: np.ndarray
+    rhat: np.ndarray
+    ess: np.ndarray
+    ess_truncated: np.ndarray
+    autocorr: np.ndarray
+    chain_mean: np.ndarray
+    chain_var: np.ndarray
+    n_series: int
+    n_per_series: int
+
+
+def summarize_draws(draws, split=True, max_lag=32, chain_ids=None) -> Summary:
+    """mean, sd, within-series variance, split R-hat, ESS and autocorrelations per element of draws [n_draws, n_chains, dim], computed
+    on the GPU.  A float64 CUDA tensor is summarised where it lies; anything else goes through numpy and one upload.  chain_ids: a
+    strictly increasing list of the chains to use (default: all)."""
+    import torch
+    t = draws if isinstance(draws, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(draws, dtype=np.float64))
+    if t.dtype != torch.float64 or t.dim() != 3:
+        raise ValueError("draws must be float64 [n_draws, n_chains, dim]")
+    t = t.contiguous()
+    if not t.is_cuda:
+        t = t.cuda()
+    N, Cn, D = (int(v) for v in t.shape)
+    ids = None if chain_ids is None else np.ascontiguousarray(chain_ids, dtype=np.uint64)
+    spec = NmSummarySpec(N, Cn, D, int(bool(split)), int(max_lag), 0 if ids is None else len(ids), None if ids is None else ids.ctypes.data)
+    csel = Cn if ids is None else len(ids)
+    n, M = (N // 2, 2 * csel) if split else (N, csel)
+    lags = max(0, min(int(max_lag), n - 1))
+    shapes = dict(mean=(D,), sd=(D,), within_var=(D,), rhat=(D,), ess=(D,), ess_truncated=(D,), autocorr=(lags + 1, D),
+                  chain_mean=(M, D), chain_var=(M, D))
+    with torch.cuda.device(t.device):
+        bufs = {k: torch.empty(shapes[k], dtype=torch.int64 if k == "ess_truncated" else torch.float64, device=t.device)
+                for k in SUMMARY_OUTPUTS}
+        out = NmSummaryOutputs()
+        for k, b in bufs.items():
+            setattr(out, "d_" + k, b.data_ptr() or None)
+        torch.cuda.current_stream(t.device).synchronize()       # the call runs on the null stream: the rows must be there
+        L = _lib.load()
+        _lib.check_status(L.nm_summarize_draws(C.byref(spec), C.c_void_p(t.data_ptr() or None), C.byref(out), None), L.nm_summary_last_error)
+        torch.cuda.synchronize(t.device)
+    host = {k: b.cpu().numpy() for k, b in bufs.items()}
+    host["ess_truncated"] = host["ess_truncated"].astype(np.uint64)
+    return Summary(n_series=M, n_per_series=n, **host)
 
 
 def sample(settings: DiagNutsSettings, logp: LogpSpec, x0=None, chain_id_offset=0, device=-1, chunk_bytes=0, expanded=False):
