@@ -1,5 +1,5 @@
 """Which kernel family is fastest for small chains, by density class, dim bucket and chain count: the measurements behind
-nm_engine_create's selection rule (csrc/nuts_engine.hip, "measured crossovers").  Families: one chain per wavefront (wave), 8 / 4 / 2 chains per
+the engine's selection rule (csrc/engine_plan.hpp: small_chain_rule and the comment above it, applied by plan_engine).  Families: one chain per wavefront (wave), 8 / 4 / 2 chains per
 wavefront (group), one chain per lane (lane, dim <= 10).  For every (density, dim, chains): post-warm-up leapfrogs/s of each family that applies and
 what the automatic rule picked.  One JSON document on stdout / --out.
 
