@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define NM_ABI_VERSION 18
+#define NM_ABI_VERSION 19
 
 typedef enum nm_status {
     NM_OK = 0,
@@ -708,7 +708,7 @@ const char* nm_pooled_last_error(void);
  * 2T + 1 <= L: stop at the first P_T that is not > 0, else P = min(P_T, prev), prev = P, tau += 2 P.   ess = (M * n) / tau.
  * ess_truncated = 1 when the loop ran out of lags without meeting a non-positive pair: the reported ESS is then an over-estimate
  * (the caller asked for too few lags).  There is no log10 cap on the ESS.  A constant column gives the NaN that IEEE arithmetic
- * gives (0 / 0 in rhat and rho).  Rank-normalisation, nested R-hat and quantiles are OUT OF SCOPE.
+ * gives (0 / 0 in rhat and rho).  Quantiles are nm_quantile_draws (below); rank-normalisation and nested R-hat are OUT OF SCOPE.
  *
  * Outputs: device pointers, any may be NULL.  d_mean = gm, d_within_var = W, d_autocorr = rho [L+1][dim], d_chain_mean /
  * d_chain_var = mean_m / var_m [M][dim].  Asynchronous on `stream` when h_chain_ids is NULL; WITH chain ids the call uploads them and
@@ -749,6 +749,58 @@ typedef struct nm_summary_outputs {          /* device pointers, any may be NULL
 } nm_summary_outputs;
 nm_status nm_summarize_draws(const nm_summary_spec* spec, const double* d_draws, const nm_summary_outputs* out, void* stream);
 const char* nm_summary_last_error(void);
+
+/* ---------------------------------------------------------------------------------------------
+ * Posterior quantiles of a recorded trace (ABI v19): exact order statistics per element, pooled over draws and chains, computed
+ * where the trace lies.  NO reference counterpart (nutpie leaves this to ArviZ on the host): defined by THIS repository, DESIGN §28;
+ * the positions are numpy's "linear" ones (Hyndman & Fan type 7).  Engine-free, a post-pass like nm_summarize_draws.
+ *
+ * Input: d_draws[n_draws][n_chains][dim], f64, row-major.  h_chain_ids (host, strictly increasing, < n_chains) selects C' =
+ * n_chain_ids chains; NULL = all chains (C' = n_chains).  Per element d the pooled sample is the n = n_draws * C' values of column d.
+ * Order: key(x) = bits(x) ^ (sign bit set ? 0xFFFFFFFFFFFFFFFF : 0x8000000000000000), compared as unsigned 64-bit integers, so that
+ *   -inf < ... < -0.0 < +0.0 < ... < +inf.   x_(r) is the value whose key has rank r (0-based; ties in any order: equal keys are
+ *   equal bits).
+ * Probabilities: h_probs[n_probs] on the host, 1 <= n_probs <= NM_QUANTILE_MAX_PROBS, every p in [0, 1]; they need not be sorted and
+ *   may repeat; the outputs come in the given order.
+ * Rank, per p, the same for every column, every operation ONE binary64 operation:
+ *   h = p * (double)(n - 1);   lo = floor(h);   g = h - lo;   hi = min(lo + 1, n - 1).
+ * Value: q = x_(lo) when g == 0 or key(x_(lo)) == key(x_(hi)); otherwise q = x_(lo) + g * (x_(hi) - x_(lo)) — one subtraction, one
+ *   multiplication, one addition, no fused multiply-add; an infinite neighbour gives what IEEE arithmetic gives (-inf and +inf: NaN).
+ * NaN: a column that holds any NaN gives NaN for every probability; d_nan_count[d] is the number of NaNs of column d.
+ * The result is built from integer counts alone (a radix selection over the keys, most significant byte first: 8 passes over the
+ * trace whatever the data): the same trace gives the same bits whatever the grid or the order in which blocks arrive, and
+ * tests/quantile_ref.py restates the definition in numpy with the same bits.
+ *
+ * Outputs: device pointers; d_quantiles[n_probs][dim], d_nan_count uint64_t[dim]; either may be NULL, not both.
+ * Asynchronous on `stream` when h_chain_ids is NULL; WITH chain ids the call uploads them and waits for `stream`
+ * (hipStreamSynchronize) before it returns — it then blocks and cannot be issued on a stream that is being captured.  h_probs is free
+ * on return in both cases: the ranks derived from it (lo, hi, g) travel in the KERNEL ARGUMENTS, nothing of it is uploaded.
+ * Scratch (stream-ordered, freed behind the kernels): dim x R x 1032 bytes + dim x (8 R + 8) bytes, R <= 2 n_probs the number of
+ * distinct ranks asked for.
+ * NM_ERR_INVALID_ARG — decided before any device call — for: a null spec / draws / outputs / h_probs; both outputs NULL; dim, n_chains
+ * or n_draws == 0; n_probs == 0 or above NM_QUANTILE_MAX_PROBS; a p that is NaN or outside [0, 1]; chain ids not strictly increasing
+ * or out of range (n_chain_ids == 0 with ids given); n above 2^32 - 1 (the counts are 32-bit); dim above 2^31 - 1 (the launch grid).
+ * h_chain_ids and d_nan_count are void* for the reason given at nm_summary_spec.  nm_quantile_last_error: the message of this call's
+ * last failure on the calling thread.
+ * ------------------------------------------------------------------------------------------- */
+#define NM_QUANTILE_MAX_PROBS 16
+typedef struct nm_quantile_spec {
+    uint64_t n_draws;
+    uint64_t n_chains;
+    uint64_t dim;
+    uint64_t n_probs;              /* 1 .. NM_QUANTILE_MAX_PROBS */
+    const double* h_probs;         /* [n_probs] on the host, only read, free on return */
+    uint64_t n_chain_ids;          /* ignored when h_chain_ids is NULL */
+    void* h_chain_ids;             /* const uint64_t[n_chain_ids] on the host, only read; NULL = all chains */
+    uint64_t reserved[2];
+} nm_quantile_spec;
+typedef struct nm_quantile_outputs {         /* device pointers, either may be NULL */
+    double* d_quantiles;     /* [n_probs][dim] */
+    void* d_nan_count;       /* uint64_t[dim] */
+    uint64_t reserved[2];
+} nm_quantile_outputs;
+nm_status nm_quantile_draws(const nm_quantile_spec* spec, const double* d_draws, const nm_quantile_outputs* out, void* stream);
+const char* nm_quantile_last_error(void);
 
 const char* nm_last_error(void);
 uint64_t    nm_abi_version(void);

@@ -328,6 +328,18 @@ inline void summarize_draws(const double* d_draws, uint64_t n_draws, uint64_t n_
     if (st != NM_OK) throw NutsError(st, nm_summary_last_error());
 }
 
+// Exact posterior quantiles of a trace that lies on the device (nm_quantile_draws; defined in nuts_amd.h): per element the order
+// statistics of all draws of all (selected) chains at numpy's "linear" positions.  out.d_quantiles is [probs.size()][dim], out.d_nan_count
+// uint64_t[dim]; either may be null.  `probs` may be freed on return; asynchronous on `stream` unless chain_ids is given.
+inline void quantile_draws(const double* d_draws, uint64_t n_draws, uint64_t n_chains, uint64_t dim, const std::vector<double>& probs,
+                           const nm_quantile_outputs& out, const std::vector<uint64_t>* chain_ids = nullptr, void* stream = nullptr) {
+    nm_quantile_spec spec{};
+    spec.n_draws = n_draws; spec.n_chains = n_chains; spec.dim = dim; spec.n_probs = probs.size(); spec.h_probs = probs.data();
+    if (chain_ids) { spec.n_chain_ids = chain_ids->size(); spec.h_chain_ids = const_cast<uint64_t*>(chain_ids->data()); }
+    const nm_status st = nm_quantile_draws(&spec, d_draws, &out, stream);
+    if (st != NM_OK) throw NutsError(st, nm_quantile_last_error());
+}
+
 struct ChainProgress {             // src/sampler.rs:1009-1051
     uint64_t finished_draws = 0, total_draws = 0, divergences = 0;
     bool tuning = true, started = false;

@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "nm_lowrank_transform_batch", "nm_engine_set_positions_masked", "nm_engine_init_positions_retry",
     "nm_init_positions_uniform_at", "nm_engine_tile_launches", "nm_engine_lockstep_launches", "nm_engine_reduce_order", "nm_engine_host_logp_calls", "nm_pooled_partials", "nm_pooled_exchange", "nm_pooled_finish", "nm_pooled_last_error",
     "nm_logp_expanded_dim", "nm_engine_expanded_dim", "nm_engine_expand", "nm_summarize_draws", "nm_summary_last_error",
+    "nm_quantile_draws", "nm_quantile_last_error",
     # the per-vector `Math` seam
     "nm_math_create", "nm_math_destroy", "nm_math_dim", "nm_math_threads", "nm_math_last_error", "nm_vec_new", "nm_vec_free", "nm_vec_read_from_slice", "nm_vec_write_to_slice", "nm_vec_copy_into", "nm_vec_fill_array", "nm_vec_array_recip", "nm_vec_axpy_out", "nm_vec_axpy", "nm_vec_array_mult", "nm_vec_array_vector_dot", "nm_vec_scalar_prods3", "nm_vec_array_gaussian", "nm_vec_array_update_variance", "nm_vec_array_update_var_inv_std_draw_grad", "nm_vec_array_update_var_inv_std_grad", "nm_vec_array_update_var_inv_std_draw", "nm_vec_array_sum_ln", "nm_vec_array_all_finite", "nm_vec_logp_array", "nm_vec_sq_norm_sum", "nm_vec_std_norm_flow", "nm_vec_std_norm_grad_flow", "nm_vec_esh_momentum_update", "nm_vec_array_normalize",
 ]
@@ -109,6 +110,18 @@ class NmSummarySpec(C.Structure):
 
 class NmSummaryOutputs(C.Structure):
     _fields_ = [("d_" + k, C.c_void_p) for k in SUMMARY_OUTPUTS] + [("reserved", C.c_uint64 * 3)]
+
+
+NM_QUANTILE_MAX_PROBS = 16
+
+
+class NmQuantileSpec(C.Structure):
+    _fields_ = [("n_draws", C.c_uint64), ("n_chains", C.c_uint64), ("dim", C.c_uint64), ("n_probs", C.c_uint64), ("h_probs", C.c_void_p),
+                ("n_chain_ids", C.c_uint64), ("h_chain_ids", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+class NmQuantileOutputs(C.Structure):
+    _fields_ = [("d_quantiles", C.c_void_p), ("d_nan_count", C.c_void_p), ("reserved", C.c_uint64 * 2)]
 
 
 # nm_lowrank_estimator_fn
@@ -279,6 +292,8 @@ def load():
     L.nm_pooled_last_error.restype = C.c_char_p
     L.nm_summarize_draws.argtypes = [C.POINTER(NmSummarySpec), vp, C.POINTER(NmSummaryOutputs), vp]
     L.nm_summary_last_error.restype = C.c_char_p
+    L.nm_quantile_draws.argtypes = [C.POINTER(NmQuantileSpec), vp, C.POINTER(NmQuantileOutputs), vp]
+    L.nm_quantile_last_error.restype = C.c_char_p
     L.nm_last_error.restype = C.c_char_p
     L.nm_abi_version.restype = u64
     for name in ABI_SYMBOLS:

@@ -18,7 +18,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import (NmDrawOutputs, NmEngineConfig, NmLogpSpec, NmSettings, NmSummaryOutputs, NmSummarySpec, NutsAmdError, STATS_DTYPE,
+from ._lib import (NmDrawOutputs, NmEngineConfig, NmLogpSpec, NmQuantileOutputs, NmQuantileSpec, NmSettings, NmSummaryOutputs, NmSummarySpec, NutsAmdError, STATS_DTYPE,
                    SUMMARY_OUTPUTS, VECTOR_STATS, check)
 
 LOGP_IID_NORMAL, LOGP_DIAG_NORMAL, LOGP_FUNNEL, LOGP_EIGHT_SCHOOLS, LOGP_MVN_PREC, LOGP_MODULE, LOGP_HOST_CALLBACK = 0, 1, 2, 3, 4, 5, 6
@@ -528,10 +528,12 @@ class ChainBatch:
         self.synchronize()
         return out if is_tensor else out.cpu().numpy()
 
-    def draw_summary(self, n_draws, expanded=False, split=True, max_lag=32):
+    def draw_summary(self, n_draws, expanded=False, split=True, max_lag=32, quantiles=None):
         """n_draws draws of every chain into device buffers, summarised where they lie (summarize_draws): returns (Summary, stats
         [n_draws, n_chains] on the host).  Chains whose last chain_status is not NM_CHAIN_OK are left out of the summary.
-        expanded=True summarises the expanded draws instead of the positions.  No position row crosses PCIe."""
+        expanded=True summarises the expanded draws instead of the positions.  No position row crosses PCIe.
+        quantiles: a list of probabilities; the Summary then also carries `quantiles` [len(quantiles), dim] (quantile_draws over
+        the same buffers and the same chains) and `quantile_probs`.  None (the default): neither is computed."""
         import torch
         dev = torch.device("cuda", self._device)                # the engine's device, whatever torch's current one is
         pos = torch.empty((n_draws, self.n_chains, self.logp.dim), dtype=torch.float64, device=dev)
@@ -549,7 +551,11 @@ class ChainBatch:
         good = np.flatnonzero(stats["chain_status"][-1] == 0)
         stats[stats["chain_status"] == np.uint64(2**64 - 1)] = np.zeros((), dtype=STATS_DTYPE)       # unwritten rows read as in draw_many
         ids = None if len(good) == self.n_chains else good
-        return summarize_draws(ex if expanded else pos, split=split, max_lag=max_lag, chain_ids=ids), stats
+        summary = summarize_draws(ex if expanded else pos, split=split, max_lag=max_lag, chain_ids=ids)
+        if quantiles is not None:
+            summary.quantile_probs = np.array(quantiles, dtype=np.float64)
+            summary.quantiles, _ = quantile_draws(ex if expanded else pos, summary.quantile_probs, chain_ids=ids)
+        return summary, stats
 
     # ---- the low-rank transformation (LowRankNutsSettings; reference src/transform/low_rank.rs) ----
     def set_transform(self, stds, mean, vals, vecs, mu_low_rank):
@@ -645,6 +651,8 @@ class Summary:
     chain_var: np.ndarray
     n_series: int
     n_per_series: int
+    quantiles: np.ndarray = None          # [n_probs, dim]; only from draw_summary(..., quantiles=[...])
+    quantile_probs: np.ndarray = None
 
 
 def summarize_draws(draws, split=True, max_lag=32, chain_ids=None) -> Summary:
@@ -679,6 +687,34 @@ def summarize_draws(draws, split=True, max_lag=32, chain_ids=None) -> Summary:
     host = {k: b.cpu().numpy() for k, b in bufs.items()}
     host["ess_truncated"] = host["ess_truncated"].astype(np.uint64)
     return Summary(n_series=M, n_per_series=n, **host)
+
+
+def quantile_draws(draws, probs, chain_ids=None):
+    """Exact quantiles per element of draws [n_draws, n_chains, dim], pooled over draws and chains, at numpy's "linear" positions
+    (nm_quantile_draws, include/nuts_amd.h), computed on the GPU: returns (quantiles [len(probs), dim], nan_count [dim]).  A column
+    with a NaN gives NaN.  A float64 CUDA tensor is read where it lies; anything else goes through numpy and one upload.  chain_ids: a
+    strictly increasing list of the chains to use (default: all)."""
+    import torch
+    t = draws if isinstance(draws, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(draws, dtype=np.float64))
+    if t.dtype != torch.float64 or t.dim() != 3:
+        raise ValueError("draws must be float64 [n_draws, n_chains, dim]")
+    t = t.contiguous()
+    if not t.is_cuda:
+        t = t.cuda()
+    N, Cn, D = (int(v) for v in t.shape)
+    p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+    ids = None if chain_ids is None else np.ascontiguousarray(chain_ids, dtype=np.uint64)
+    spec = NmQuantileSpec(N, Cn, D, len(p), p.ctypes.data if len(p) else None, 0 if ids is None else len(ids),
+                          None if ids is None else ids.ctypes.data)
+    with torch.cuda.device(t.device):
+        q = torch.empty((len(p), D), dtype=torch.float64, device=t.device)
+        nan = torch.empty((D,), dtype=torch.int64, device=t.device)
+        out = NmQuantileOutputs(q.data_ptr() or None, nan.data_ptr() or None)
+        torch.cuda.current_stream(t.device).synchronize()       # the call runs on the null stream: the rows must be there
+        L = _lib.load()
+        _lib.check_status(L.nm_quantile_draws(C.byref(spec), C.c_void_p(t.data_ptr() or None), C.byref(out), None), L.nm_quantile_last_error)
+        torch.cuda.synchronize(t.device)
+    return q.cpu().numpy(), nan.cpu().numpy().astype(np.uint64)
 
 
 def sample(settings: DiagNutsSettings, logp: LogpSpec, x0=None, chain_id_offset=0, device=-1, chunk_bytes=0, expanded=False):
