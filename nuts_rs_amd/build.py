@@ -20,7 +20,7 @@ UNITS = ["kern_tile_mvn_prec.hip", "kern_tile_mvn_diag.hip", "kern_lockstep.hip"
          "kern_lr_host_cb.hip@large", "kern_lr_host_cb.hip@small", "kern_kin_iid_normal.hip@large", "kern_kin_iid_normal.hip@small", "kern_kin_diag_normal.hip@large",
          "kern_kin_diag_normal.hip@small", "kern_kin_funnel.hip@large", "kern_kin_funnel.hip@small", "kern_kin_host_cb.hip@large", "kern_kin_host_cb.hip@small", "kern_lane.hip",
          "kern_lane_kin.hip", "kern_iid_normal.hip@large", "kern_iid_normal.hip@small", "kern_diag_normal.hip@large", "kern_diag_normal.hip@small", "kern_funnel.hip@large",
-         "kern_funnel.hip@small", "kern_host_cb.hip@large", "kern_host_cb.hip@small", "nuts_engine.hip", "kern_cluster.hip", "kern_cluster_kin.hip", "kern_eight_schools.hip@inl",
+         "kern_funnel.hip@small", "kern_host_cb.hip@large", "kern_host_cb.hip@small", "unit_batch.hip", "nuts_engine.hip", "kern_cluster.hip", "kern_cluster_kin.hip", "kern_eight_schools.hip@inl",
          "kern_lr_eight_schools.hip@inl", "kern_kin_eight_schools.hip@inl", "math_seam.hip", "probe_bw.hip", "pooled_reduce.hip", "lowrank_device.hip", "kern_expand.hip@inl", "summary.hip", "quantile.hip", "lowrank_host.cpp"]
 # (lowrank_host.cpp holds both ISA builds of the host estimator in ONE translation unit: per-function target attributes, see there)
 # Variants of a unit ("file@variant": its own object, the flags below).  A density's one-chain kernels are TWO units from one source
@@ -30,7 +30,6 @@ UNITS = ["kern_tile_mvn_prec.hip", "kern_tile_mvn_diag.hip", "kern_lockstep.hip"
 # (kern_expand.hip, the expansion pass: nuts_expand.hpp).
 VARIANT_FLAGS = {"": [], "small": ["-DNM_TU_PART=1", "-DNM_DETMATH_INLINE=1"], "large": ["-DNM_TU_PART=2"], "inl": ["-DNM_DETMATH_INLINE=1"]}
 NO_CALL_VARIANTS = ("small", "inl")
-HEADERS = ["nuts_kernels.hpp", "nuts_adapt.hpp", "nuts_launch.hpp", "dev_math.hpp", "detmath_tables.hpp", "zig_tables.hpp", "nuts_group.hpp", "nuts_group_impl.hpp", "nuts_tile.hpp", "nuts_expand.hpp", os.path.join("..", "..", "include", "nuts_amd.h")]
 # -ffp-contract=off: FMAs only where the reference writes mul_add
 # -Wno-pass-failed: "loop not unrolled" remarks of the matrix-core kernel's partially unrolled product loops (a diagnostic only)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-pass-failed"]
@@ -203,7 +202,6 @@ def build(force=False, verbose=False, extra_flags=(), scan=True):
         return LIB
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(OBJ, exist_ok=True)
-    hdrs = [os.path.join(CSRC, h) for h in HEADERS]
 
     def compile_unit(u):
         src, obj = _src(u), _obj(u)

@@ -13,6 +13,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "nuts_contract.hpp"   // CL_MAX_MEMBERS, NM_MF_MAX_MD: limits the host plans with
 #include "detmath_tables.hpp"
 
 namespace nm {
@@ -157,7 +158,6 @@ constexpr int RED_MAX_VALUES = 6;
 #ifndef NM_CLUSTER_MODE
 #define NM_CLUSTER_MODE 0
 #endif
-constexpr int CL_MAX_MEMBERS = 32;          // blocks per chain at most (dim <= 32 x 4096): the members of a chain share an XCD, which has 32 CUs
 constexpr int CL_BOX_WORDS = 6;              // u64 words of a chain's mailbox per (member, value): [2][k][V] counted + [2][k][2 V] tagged
 struct ClusterLink {
     unsigned long long* box;     // [2][k][RED_MAX_VALUES] bit patterns of the members' partial sums (two epochs alternate), then
@@ -722,7 +722,6 @@ static __host__ __device__ NM_DM_CALL MergeOut merge_math_main(double a, double 
 // the log of the draw's leaf weights (mf_fold / mf_fold_main) and calls merge_math / merge_math_main on it.
 // Portable arithmetic only (f32 fma polynomials, exponent insertion): the host runs the device's operation sequence, and
 // tests/cpp/merge_filter_check.hip measures the errors the derivation uses.
-constexpr int NM_MF_MAX_MD = 12;                  // deepest layout (maxdepth + extra_doublings) the bound below is derived for: 2 * 12 + 2 = 26 merges in a chain
 constexpr uint32_t NM_MF_FORCE_BITS = 8;          // a merge whose Bernoulli word has this many zero low bits takes the exact path whatever the filter says
 constexpr uint32_t NM_MF_UNDECIDED = 8u;          // flag bit 3 of merge_filter_impl's answer
 constexpr double NM_MF_ETA_E = 2e-7;              // mf_exp: relative error against exp_sl on every f32 in [-40, 0]            (measured 9.0e-8)

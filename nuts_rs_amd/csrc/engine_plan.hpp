@@ -2,35 +2,25 @@
 // scratch layout (plan_engine), whether a transformation given from outside runs on the matrix cores (plan_transform), and which launches
 // serve a draw call (plan_draw).  Host code, pure: no HIP call, no getenv, no global, no allocation.  What the device has to say — the
 // compute-unit count and the kernels' occupancies — reaches plan_engine through DeviceFacts, which nuts_engine.hip backs with the
-// kernels' query launches and tests/cpp/engine_plan_check.hip with constants.  The kernel headers are included for their constants and
-// size functions only.  DESIGN.md's table of kernel families ("selected when") describes what this file computes.
+// kernels' query launches and tests/cpp/engine_plan_check.hip with constants.  What the kernels fix — layouts, depth limits, size rules —
+// comes from nuts_contract.hpp.  DESIGN.md's table of kernel families ("selected when") describes what this file computes.
 #pragma once
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <string>
 
-#include "nuts_launch.hpp"
-#include "nuts_lane.hpp"
-
-// chains per block of the matrix-core kernels and their blocks per compute unit (nuts_tile.hpp, which switches its whole translation
-// unit to tile mode and is therefore not included here; tuning builds pass both to all units)
-#ifndef NM_TILE_CHAINS
-#define NM_TILE_CHAINS 16
-#endif
-#ifndef NM_TILE_OCC
-#define NM_TILE_OCC 1
-#endif
+#include "nuts_contract.hpp"
+#include "dev_math.hpp"       // dlog, u2d, d2u: the restated logarithm of ln_max_step and the jitter scale
 
 namespace nm {
 namespace plan {
 
-constexpr uint64_t NM_LOCK_MAXDEPTH = 11;            // nuts_lockstep.hpp LOCK_MAXDEPTH
 constexpr uint64_t NM_LANE_EARLY_GROUP_DRAWS = 20;   // an engine that chose the one-chain-per-lane kernels by itself runs this many first warm-up draws 8 chains per wavefront
 constexpr uint64_t CL_SLICE = 4096;                  // elements of a chain one block owns when the chain is wider than one block
 
 // The instantiation family of the one-chain-per-block kernels.  The VALUES are ABI: a density module built with NM_MODULE_VARIANTS receives
-// them as the `variant` argument of nm_module_launch_variant, next to a KernelKind (nuts_launch.hpp) whose ORDER is ABI for the same reason.
+// them as the `variant` argument of nm_module_launch_variant, next to a KernelKind (nuts_contract.hpp) whose ORDER is ABI for the same reason.
 // Neither may be renumbered without a new NM_ABI_VERSION.
 enum KernelFamily : int {
     FAMILY_PLAIN = 0,         // Density
@@ -150,7 +140,7 @@ inline EnginePlan plan_engine(const PlanInput& in, nm_status* status, std::strin
     nm_settings s = in.s;
     const nm_engine_config& cfg = in.cfg;
     const uint64_t kind = in.logp_kind, dim = in.dim, n_chains = in.n_chains;
-    // (the tree's slot families and pend tables are laid out for maxdepth + extra_doublings levels: nuts_kernels.hpp layout_depth)
+    // (the tree's slot families and pend tables are laid out for maxdepth + extra_doublings levels: nuts_contract.hpp layout_depth)
     if (s.maxdepth > (uint64_t)MAX_MAXDEPTH || s.extra_doublings > (uint64_t)MAX_MAXDEPTH || s.maxdepth + s.extra_doublings > (uint64_t)MAX_MAXDEPTH)
         NM_PLAN_REFUSE(NM_ERR_UNSUPPORTED, "maxdepth %llu + extra_doublings %llu > %d", (unsigned long long)s.maxdepth, (unsigned long long)s.extra_doublings, MAX_MAXDEPTH);
     if (s.step_size_method > NM_STEP_FIXED) NM_PLAN_REFUSE(NM_ERR_INVALID_ARG, "step_size_method %llu is not one of NM_STEP_*", (unsigned long long)s.step_size_method);
@@ -212,10 +202,8 @@ inline EnginePlan plan_engine(const PlanInput& in, nm_status* status, std::strin
     p.lr = lr; p.kin = kin; p.mclmc = mclmc;
     p.dpl = dpl; p.wpc = wv; p.cl_k = cl_k;
     p.family = cl_k > 1 ? (kin ? FAMILY_CLUSTER_KINETIC : FAMILY_CLUSTER) : lr ? FAMILY_LOW_RANK : (kin ? FAMILY_KINETIC : FAMILY_PLAIN);
-    // (the condition of has_sampling_build, on this side of the launch interface; whether the launches are this family's at all —
-    // not the lane / group / matrix-core kernels — is decided in plan_draw)
-    p.sampling_build = p.family == FAMILY_PLAIN && wv == 1 && (dpl == 8 || dpl == 16) &&
-                       (kind == NM_LOGP_IID_NORMAL || kind == NM_LOGP_DIAG_NORMAL || kind == NM_LOGP_FUNNEL || kind == NM_LOGP_MVN_PREC) &&
+    // (whether the launches are this family's at all — not the lane / group / matrix-core kernels — is decided in plan_draw)
+    p.sampling_build = p.family == FAMILY_PLAIN && sampling_tiling(dpl, wv) && sampling_logp_kind(kind) &&
                        layout_depth(s) <= NM_MF_MAX_MD;      // (deeper layouts than its merge filter's error bound covers stay on the general kernel)
     const uint64_t dpad = 64ull * (uint64_t)dpl * (uint64_t)wv;
     p.dpad = dpad;
@@ -362,7 +350,7 @@ inline TransformPlan plan_transform(const EnginePlan& p, bool per_chain, uint64_
         t.tile = true;
         // chain_tiles: 0 = the lockstep kernel where it applies, else the one-wavefront-per-chain tile kernel; 2 = always the latter;
         // 3 = the lockstep kernel or an error
-        const bool lock_ok = s.maxdepth >= 1 && s.maxdepth + s.extra_doublings <= NM_LOCK_MAXDEPTH;
+        const bool lock_ok = s.maxdepth >= 1 && s.maxdepth + s.extra_doublings <= (uint64_t)lock::LOCK_MAXDEPTH;
         // (an engine whose settings ask for the divergence / mass-matrix vectors — outputs the lockstep kernel does not write —
         // takes the tile kernel when the choice is automatic; an explicit chain_tiles = 3 keeps the lockstep kernel and its error)
         const bool wants_vectors = s.store_divergences || s.store_mass_matrix;

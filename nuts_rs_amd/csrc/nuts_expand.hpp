@@ -13,6 +13,7 @@
 // by the functor itself, one chunk of a row's outputs per block.  Blocks stride over the tiles; the grid is bounded by the caller.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "nuts_contract.hpp"
 #include "nuts_kernels.hpp"
 
 namespace nm {
@@ -123,8 +124,4 @@ inline hipError_t launch_expand_t(const double* d_params, uint64_t dim, uint64_t
     }
 }
 
-// kern_expand.hip: the built-in densities.  *has_kernel = 0: the expansion is the identity (edim == dim)
-uint64_t builtin_expanded_dim(uint64_t logp_kind, uint64_t dim, const double* h_params, uint64_t n_params, int* has_kernel);
-hipError_t launch_expand(uint64_t logp_kind, const double* d_params, uint64_t dim, uint64_t edim, uint64_t n_rows, const double* d_positions,
-                         double* d_expanded, unsigned grid_cap, hipStream_t stream);
 }  // namespace nm

@@ -16,15 +16,13 @@
 // The implementation (nuts_group_impl.hpp) is compiled once per group size into namespaces grp8 / grp16 / grp32.
 #pragma once
 #include <type_traits>
+#include "nuts_contract.hpp"
 #include "nuts_kernels.hpp"
 
 namespace nm {
 namespace grp {
-constexpr int GMAXDEPTH = 10;
 constexpr int NM_GROUP_OCC = 2;       // waves per SIMD the sampling kernel's register allocation leaves room for (3: spills, slower)
 constexpr int NM_GROUP_OCC_TUNE = 2;  // ... and the warm-up kernel's (1 measured on K4's 8192-chain shard, where one wavefront per SIMD is resident anyway: see DESIGN §8)
-// lanes per chain for a dim (0: no group form)
-__host__ __device__ inline int group_size(uint64_t dim) { return dim <= 16 ? 8 : dim <= 32 ? 16 : dim <= 64 ? 32 : 0; }
 }  // namespace grp
 }  // namespace nm
 

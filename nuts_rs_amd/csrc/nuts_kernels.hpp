@@ -22,12 +22,11 @@
 //   src/stepsize/adapt.rs:52-272, src/stepsize/dual_avg.rs:34-166, src/chain.rs:137-188.
 #pragma once
 #include <type_traits>
+#include "nuts_contract.hpp"  // the layouts (PSlot, SSlot, slot_*), ChainScalars, KParams, CbMail, the depth limits: what the host shares
 #include "dev_math.hpp"
 #include "../../include/nuts_amd.h"
 
 namespace nm {
-
-constexpr int MAX_MAXDEPTH = 20;
 
 // LDS residency (the tile header sets 0): which tree end points of the resident chain stay on the CU
 #ifndef NM_LDS_L1
@@ -38,39 +37,6 @@ constexpr int MAX_MAXDEPTH = 20;
 constexpr int NM_CHECK_GROUP = 2;
 #define NM_GROUP_BARRIER(m) do { if (((m) + 1) % NM_CHECK_GROUP == 0) __builtin_amdgcn_sched_barrier(0); } while (0)
 
-// ---------------------------------------------------------------------------------------------
-// HBM layout.
-//   pvec[chain][PSlot][DP]  : what a chain owns between draws
-//   svec[wave][scratch][DP] : tree scratch of a resident wave
-// ---------------------------------------------------------------------------------------------
-enum PSlot : int {
-    P_X = 0, P_GX, P_Z, P_GZ,          // current point (TransformedPoint, transformed_hamiltonian.rs:56-77)
-    P_SIG, P_ISIG, P_MU,               // DiagMassMatrix stds / inv_stds / mean (transform/diagonal.rs:9-17)
-    E_DM, E_DV, E_GM, E_GV,            // foreground RunningVariance of draws / grads (adapt/diagonal.rs:108-115)
-    B_DM, B_DV, B_GM, B_GV,            // background
-    P_V,                               // MclmcChain: the momentum survives from draw to draw (src/mclmc.rs:551)
-    NUM_PSLOT
-};
-// main-tree edges: `left` and `right` are edge ids 0/1 (both start as the initial point's id 0; a successful doubling
-// writes the new edge to the id this side owns alone, or to id 1 while both sides still share id 0).  Only the g_z of
-// an edge lives here (EDGEn_G); its (z, v) stay in LDS (BlockShared::edge_z / edge_v).
-enum SSlot : int { EDGE0_Z = 0, EDGE0_V, EDGE0_G, EDGE1_Z, EDGE1_V, EDGE1_G, EDGE2_Z, EDGE2_V, EDGE2_G, STAGE_V, S_DYN };
-__host__ __device__ inline int slot_edge(int id) { return EDGE0_Z + 3 * id; }
-// dynamic scratch: F[k] (z,v), L[k] (z,v) for k in 0..=maxdepth, then the candidate pool C[p] (z), p in 0..maxdepth+2
-__host__ __device__ inline int slot_F(int k) { return S_DYN + 2 * k; }
-__host__ __device__ inline int slot_L(int maxdepth, int k) { return S_DYN + 2 * (maxdepth + 1) + 2 * k; }
-__host__ __device__ inline int slot_C(int maxdepth, int p) { return S_DYN + 4 * (maxdepth + 1) + p; }
-__host__ __device__ inline int num_sslots(int maxdepth) { return S_DYN + 4 * (maxdepth + 1) + (maxdepth + 3); }
-// Batched merges (DPL <= 4, one wave per chain; see resolve_chunk): the z of the last NM_RING leaves, one slot per leaf (leaf n of
-// a doubling lives in slot n mod NM_RING), behind the slots above.  The host adds NM_RING to nsslot for these tilings.
-constexpr int NM_RING = 64;
-__host__ __device__ inline int slot_R(int maxdepth, int i) { return num_sslots(maxdepth) + i; }
-// The depth every slot family (F, L, candidate pool, pend tables) is laid out for.  A tree that turned at depth d <= maxdepth is extended by
-// `extra_doublings` further doublings (src/nuts.rs:350-371), so sub-trees of level up to maxdepth + extra_doublings - 1 are built; with the
-// layout of `maxdepth` alone slot_L(MD, MD + 1) is slot_C(MD, 0) and the candidate pool overflows.
-// (Computed once by the host into KParams::layout_md: reading both settings fields in ctx_begin changed the register allocation of the
-// 16-wavefront matrix-core kernel enough to break it — the last doubling of trees deeper than 6 stopped after one leaf)
-__host__ __device__ inline int layout_depth(const nm_settings& s) { return (int)(s.maxdepth + s.extra_doublings); }
 // The one-chain-per-block kernels of a plain unit: the matrix-core (tile) and several-blocks-per-chain (cluster) units are register-capped
 // and keep the forms of rounds 1-4 throughout.
 constexpr bool plain_unit = !NM_TILE_MODE && !NM_CLUSTER_MODE;
@@ -79,10 +45,7 @@ constexpr bool plain_unit = !NM_TILE_MODE && !NM_CLUSTER_MODE;
 // register allocation has the room: (16 doubles, 1 wave) K2 2.02e11 -> 2.13e11, (2, 1) K3 +7 %; the register-capped tilings in between lose
 // ((8, 1): -33 %, (4, 1): -7 %: the end points go to scratch memory) and keep the slots (profiles/r05f_*).
 template <int DPL, int W> constexpr bool reg_edges() { return plain_unit && W == 1 && (DPL == 16 || DPL == 2); }
-// Batched merges (resolve_chunk): the one-wavefront tilings up to this width evaluate a doubling's merges together and keep a ring of the
-// last NM_RING leaves behind the tree's other scratch slots.  ONE predicate for the kernels and for the host's scratch layout.
-constexpr int NM_BATCH_MAX_DPL = 4;
-__host__ __device__ constexpr bool batched_merges(int dpl, int w, bool plain) { return plain && w == 1 && dpl <= NM_BATCH_MAX_DPL; }
+// Batched merges (resolve_chunk; nuts_contract.hpp batched_merges, the predicate the host's scratch layout shares) in this unit's mode
 template <int DPL, int W> constexpr bool batched_merges() { return batched_merges(DPL, W, plain_unit); }
 // Gradient-free points (round 6, "NOG": the (16 doubles, 1 wavefront) tiling with an element-wise density and the diagonal transformation: K2).
 // The launch is bound by the bytes the tree's end points move, so a point is (z, v): its transformed gradient g_z is NOT kept.
@@ -97,96 +60,6 @@ template <int DPL, int W, class Dens> constexpr bool nog_mode();
 // the top-level test has six loads per iteration and looks at most NM_TEST_CHUNK3_MAX ahead
 constexpr int NM_TEST_CHUNK = 4;
 constexpr int NM_TEST_CHUNK3_MAX = 2;
-
-// Per-chain scalars (everything of NutsChain / GlobalStrategy / stepsize::Strategy / DualAverage that is not a vector)
-struct ChainScalars {
-    uint32_t key[8];
-    uint64_t rng_pos;
-    // current point
-    double logp, logdet;
-    int64_t transform_id;
-    // mass matrix
-    double mm_logdet;
-    int64_t mm_id;
-    // hamiltonian
-    double step_size;
-    // GlobalStrategy (adapt_strategy.rs:24-39)
-    uint64_t draw_count, last_update, current_window_size, tuning, has_initial_mass_matrix;
-    // RunningVariance counts (draw and grad estimators always have equal counts)
-    uint64_t cnt_fg, cnt_bg;
-    // DualAverage (dual_avg.rs:34-41)
-    double log_step, log_step_adapted, hbar, mu;
-    uint64_t da_count;
-    // Adam (stepsize/adam.rs:42-53); its log_step shares `log_step` above
-    double adam_m, adam_v;
-    uint64_t adam_t;
-    // stepsize::Strategy last_* (stepsize/adapt.rs:58-64)
-    double last_mean_tree_accept, last_sym_mean_tree_accept, last_max_energy_error;
-    uint64_t last_n_steps;
-    uint64_t status;       // NM_CHAIN_*
-    uint64_t total_steps;  // leapfrogs since creation (metric)
-    uint64_t px_stale;     // 1: P_X / P_GX do not hold the current point (they equal what P_Z recomputes to)
-    int64_t stats_last_id; // mass-matrix id at the previous statistics extraction (chain.rs:195-200), starts at -1
-    // ---- low-rank transformation and its adaptation (NM_ADAPT_LOW_RANK; LrWrap kernels only)
-    uint64_t lr_has_inner;        // LowRankMassMatrix.inner.is_some() (low_rank.rs:112)
-    uint64_t lr_rank;             // InnerMatrix.num_eigenvalues
-    // LowRankMassMatrixStrategy (adapt/low_rank.rs:14-21): the deque is rows [lr_start, lr_start + lr_len) of the chain's
-    // window buffer; lr_split = background_split
-    uint64_t lr_start, lr_len, lr_split;
-    // hand-off with the host's estimator: 1 = GlobalStrategy::adapt paused at `mass_matrix_adapt.adapt(..)`, waiting;
-    // 2 = the host answered (lr_upd_*); 3 = a transformation from nm_engine_set_transform waits to be committed
-    uint64_t lr_pending;
-    uint64_t lr_upd_ok, lr_upd_rank;   // the answer: a finite update was uploaded (P_SIG / P_ISIG / P_MU, lrvec, lrval), its rank
-    double lr_upd_logdet;              // its -1/2 sum ln lambda (InnerMatrix::new, low_rank.rs:57)
-    uint64_t lr_is_late;               // is_late of the paused adapt call
-    uint64_t lr_row;                   // output row of the paused draw
-    // KinWrap kernels: the Hamiltonian's current KineticEnergyKind (NutsSettings::trajectory_kind; MclmcChain switches it)
-    uint64_t kin;
-};
-enum { LR_IDLE = 0, LR_WAIT_HOST = 1, LR_ANSWERED = 2, LR_SET_TRANSFORM = 3 };
-
-struct KParams {
-    nm_settings s;
-    uint64_t n_chains, dim, dpad, chain_id_offset, nsslot;
-    double* pvec;
-    double* svec;
-    ChainScalars* sc;
-    const double* zig_x;
-    const double* zig_f;
-    const double* logp_params;
-    // derived schedule constants (GlobalStrategy::new, adapt_strategy.rs:77-98)
-    uint64_t early_end, final_step_size_window;
-    uint64_t mclmc_switch_draw;        // MclmcChain::switch_draw (sampler.rs:441)
-    // chains wider than one block (NM_CLUSTER_MODE kernels): cl_k members of cl_slice elements each per chain, their mailboxes
-    uint64_t cl_k, cl_slice;
-    uint64_t cl_general;               // 1: always the general (release / acquire) exchange, never the same-XCD one (NM_CLUSTER_GENERAL=1: tests)
-    unsigned long long* cl_box;        // [clusters][2][cl_k][RED_MAX_VALUES]
-    unsigned long long* cl_cnt;        // [clusters], zeroed before every launch
-    double ln_max_step;                // ln(da_max_step_size), dual_avg.rs:59
-    double jitter_low, jitter_scale;   // Uniform::new(1-j, 1+j) (stepsize/adapt.rs:259-261)
-    // outputs of the draw kernel
-    double* out_positions;       // [n_draws][n_chains][dim] or null
-    nm_draw_stats* out_stats;    // [n_draws][n_chains] or null
-    // vector-valued statistics (nm_draw_outputs), [n_draws][n_chains][dim] or null
-    double *out_gradient, *out_tpos, *out_tgrad, *out_mm_inv, *out_mm_mu;
-    double *out_div_start, *out_div_start_grad, *out_div_end;
-    uint64_t n_draws;
-    unsigned long long* prof;    // NM_PROF builds: cycle counters of block 0 (tools/prof_phases.py)
-    const double* x0;            // init kernel: [n_chains][dim]
-    // low-rank transformation (LrWrap kernels): per chain [1 + lr_rmax][dpad] (row 0 = mu_lr, row 1 + k = eigenvector k,
-    // tile layout like every chain vector), [2][lr_rmax] (lambda^1/2, lambda^-1/2), and the window [lr_cap][2][dim]
-    double* lrvec;
-    double* lrval;
-    double* lrwin;
-    uint64_t lr_rmax, lr_cap;
-    uint64_t draw_end, row_base;  // LrWrap draw kernel: chains draw until draw_count == draw_end; output row = draw_count - row_base
-    double* out_mm_eigvals;
-    const uint8_t* init_mask;     // init kernel: chains with mask 0 are left untouched (null = all)
-    // NM_LOGP_HOST_CALLBACK: one mailbox per chain in pinned host memory (CbMail header, then x[dim], grad[dim])
-    unsigned char* cb_mail;
-    uint64_t cb_stride;           // bytes per mailbox
-    uint64_t layout_md;           // layout_depth(s) = maxdepth + extra_doublings: the depth the tree's slot families are laid out for
-};
 
 // Phase timing for development (-DNM_PROF=1): block 0 accumulates shader-clock cycles between marks into P.prof[].
 #ifndef NM_PROF
@@ -583,7 +456,6 @@ struct EightSchools {
 // publishes a sequence number (system-scope release), and polls for the answer that the engine's service threads write
 // after calling the user's function (nuts_engine.hip).  Latency ~ PCIe round trip + the callback; it exists so that any
 // CpuLogpFunc drops in, not for throughput.
-struct CbMail { uint64_t req, resp; int64_t status; double logp; };
 struct HostCb {
     static constexpr bool kNeedsLdsVector = false;
     static constexpr bool kCanFail = true;
@@ -1690,11 +1562,7 @@ NM_DEV bool mass_matrix_adapt(ChainCtx<DPL, W, Dens>& C, const Tile<DPL>& dm, co
 //   against 2.64e11 with it, 2.59e11 for the general kernel);
 //   the two uexp of a frozen log step per draw (the step size, the row's step_size_bar): taken once per chain per launch, in a register or
 //   in LDS, the value costs that kernel 13 to 35 more spilled SGPRs and up to 16 B of scratch.
-template <class Dens> constexpr bool sampling_density() {
-    return std::is_same<Dens, IidNormal>::value || std::is_same<Dens, DiagNormal>::value || std::is_same<Dens, Funnel>::value ||
-           std::is_same<Dens, MvnPrec>::value;          // (the 8 schools run on the 2-doubles tiling alone)
-}
-template <int DPL, int W, class Dens> constexpr bool has_sampling_build() { return plain_unit && W == 1 && (DPL == 8 || DPL == 16) && sampling_density<Dens>(); }
+template <int DPL, int W, class Dens> constexpr bool has_sampling_build() { return plain_unit && sampling_tiling(DPL, W) && sampling_density<Dens>(); }
 
 // GlobalStrategy::adapt (reference src/adapt_strategy.rs:121-222).  x, gx = chosen draw.
 template <int DPL, int W, class Dens, bool SAMPLING = false>

@@ -22,20 +22,11 @@
 // lane, conflict-free).
 #pragma once
 #include <type_traits>
+#include "nuts_contract.hpp"
 #include "nuts_kernels.hpp"
 
 namespace nm {
 namespace lane {
-
-constexpr int LMAXDEPTH = 10;
-// (round 5: the 8-pair kernel for dim 11 .. 16 — 2 KB of scratch per lane, slower than the 8-lane kernels at every size measured — is removed)
-__host__ __device__ inline int lane_pairs(uint64_t dim) { return dim <= 4 ? 2 : dim <= 8 ? 4 : dim <= 10 ? 5 : 0; }
-
-struct LaneParams {
-    double* lws;          // [grid][NUM_PSLOT][2 NP][64]  the chains' persistent vectors while the kernel runs
-    double* lsv;          // [grid][nslots][2 NP][64]     tree scratch
-    uint64_t nslots;
-};
 
 // ---- the engine's sum over a chain of <= 16 elements: balanced tree over the pair partials (see the header) ----
 template <int NP>

@@ -1,8 +1,9 @@
 // nuts_launch.hpp — kernel launch plumbing shared by the per-density translation units (each density's kernels
-// are compiled in their own .hip file so the build parallelises).
+// are compiled in their own .hip file so the build parallelises).  KernelKind, NM_LAUNCH_ARGS and the entry points' prototypes: nuts_contract.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
+#include "nuts_contract.hpp"
 #include "nuts_kernels.hpp"
 #include "nuts_group.hpp"
 
@@ -15,12 +16,6 @@
 #define NM_TU_PART 0
 #endif
 namespace nm {
-enum KernelKind { K_INIT, K_DRAW, K_QUERY,      // K_QUERY: resident blocks per CU of the draw kernel
-                  K_GROUP_DRAW, K_GROUP_TUNE, K_GROUP_QUERY,    // the small-chain kernels of nuts_group.hpp (dim <= 64): sampling / warm-up
-                  K_GROUP_DRAW_ROOMY, K_GROUP_TUNE_ROOMY,       // ... compiled for one wavefront per SIMD (grids of at most 4 x CUs blocks; built-in densities)
-                  K_DRAW_SAMPLING };    // the draw kernel's sampling-phase build (nuts_kernels.hpp has_sampling_build): launches whose draws all have an index > num_tune.
-                                        // (Last, so that the kinds a density module was built with keep their values; a module is never asked for this one.)
-
 // the small-chain kernels exist for the densities that have a group form (nuts_group.hpp); the group size follows P.dim
 #define NM_LAUNCH_GROUP_NS(NS)                                                                                            \
     if constexpr (!std::is_void<typename NS::GroupDensity<Dens>::type>::value) {                                          \
@@ -50,9 +45,6 @@ inline hipError_t launch_group(KernelKind kind, const KParams& P, unsigned grid_
     return hipErrorInvalidValue;
 }
 #undef NM_LAUNCH_GROUP_NS
-// grid = number of blocks (one block of 64*W threads = one resident chain); for K_QUERY *occ receives
-// hipOccupancyMaxActiveBlocksPerMultiprocessor of the draw kernel
-inline bool is_group_kind(KernelKind kind) { return kind == K_GROUP_DRAW || kind == K_GROUP_TUNE || kind == K_GROUP_QUERY || kind == K_GROUP_DRAW_ROOMY || kind == K_GROUP_TUNE_ROOMY; }
 template <int DPL, int W, class Dens>
 inline hipError_t launch_t(KernelKind kind, const KParams& P, unsigned grid_blocks, hipStream_t stream, int* occ) {
 #if NM_TU_PART != 2
@@ -112,8 +104,7 @@ inline hipError_t launch_d(int dpl, int w, KernelKind kind, const KParams& P, un
     return hipErrorInvalidValue;
 }
 
-// the entry point of a density's kernels, in kern_<density>.hip: NM_DEFINE_LAUNCH(launch_x, Density)
-#define NM_LAUNCH_ARGS int dpl, int w, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ
+// the entry point of a density's kernels, in kern_<density>.hip: NM_DEFINE_LAUNCH(launch_x, Density) (its arguments: nuts_contract.hpp NM_LAUNCH_ARGS)
 #if NM_TU_PART == 1
 #define NM_DEFINE_LAUNCH(name, ...)                                                                                       \
     hipError_t name##_large(NM_LAUNCH_ARGS);                                                                              \
@@ -126,30 +117,4 @@ inline hipError_t launch_d(int dpl, int w, KernelKind kind, const KParams& P, un
 #else
 #define NM_DEFINE_LAUNCH(name, ...) hipError_t name(NM_LAUNCH_ARGS) { return launch_d<__VA_ARGS__>(dpl, w, kind, P, grid, stream, occ); }
 #endif
-// one definition per density, in kern_<density>.hip
-hipError_t launch_iid_normal(int dpl, int w, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ);
-hipError_t launch_diag_normal(int dpl, int w, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ);
-hipError_t launch_funnel(int dpl, int w, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ);
-hipError_t launch_eight_schools(int dpl, int w, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ);
-hipError_t launch_mvn_prec(int dpl, int w, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ);
-// the same kernels with the low-rank transformation compiled in (LrWrap<Density>), in kern_lr_<density>.hip
-hipError_t launch_iid_normal_lr(int dpl, int w, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ);
-hipError_t launch_diag_normal_lr(int dpl, int w, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ);
-hipError_t launch_funnel_lr(int dpl, int w, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ);
-hipError_t launch_eight_schools_lr(int dpl, int w, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ);
-hipError_t launch_mvn_prec_lr(int dpl, int w, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ);
-// the same kernels with the non-Euclidean KineticEnergyKinds compiled in (KinWrap<Density>), in kern_kin_<density>.hip
-hipError_t launch_iid_normal_kin(int dpl, int w, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ);
-hipError_t launch_diag_normal_kin(int dpl, int w, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ);
-hipError_t launch_funnel_kin(int dpl, int w, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ);
-hipError_t launch_eight_schools_kin(int dpl, int w, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ);
-hipError_t launch_mvn_prec_kin(int dpl, int w, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ);
-hipError_t launch_host_cb_kin(int dpl, int w, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ);
-// chains wider than one block (kern_cluster.hip): dim > 4096, element-wise densities
-hipError_t launch_cluster(uint64_t logp_kind, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ);
-// ... with the non-Euclidean trajectory kinds / MCLMC (kern_cluster_kin.hip)
-hipError_t launch_cluster_kin(uint64_t logp_kind, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ);
-// NM_LOGP_HOST_CALLBACK (kern_host_cb.hip)
-hipError_t launch_host_cb(int dpl, int w, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ);
-hipError_t launch_host_cb_lr(int dpl, int w, KernelKind kind, const KParams& P, unsigned grid, hipStream_t stream, int* occ);
 }  // namespace nm

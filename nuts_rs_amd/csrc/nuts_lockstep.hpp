@@ -26,7 +26,8 @@
 // the four lane-rows of a stripe, stripes in ascending order — which the oracle reproduces (MathCfg.tile_order; the reference's
 // own order is its SIMD width's).  Every elementwise operation is the one-chain kernel's.
 #pragma once
-#include "nuts_tile.hpp"     // tile mode, TileMats, taddr, v4d; nuts_kernels.hpp
+#include "nuts_contract.hpp"
+#include "nuts_tile.hpp"     // tile mode, taddr, v4d; nuts_kernels.hpp (and with it nuts_contract.hpp: TileMats, LOCK_MAXDEPTH)
 #include "nuts_lane.hpp"     // the per-lane scalar toolkit: lexp / llogaddexp, LMath, LRng, LAccept
 
 namespace nm {
@@ -49,7 +50,7 @@ constexpr int LWV = LS / SPW;      // wavefronts per block
 constexpr int LROWS = 256;         // rows of a column tile (dim, rank <= 256)
 constexpr int NRED = 32;           // partial-sum slots per (stripe, chain) and reduction pass
 constexpr int GROUPS_PER_PASS = 4; // U-turn test groups (6 sums each) per pass
-constexpr int LOCK_MAXDEPTH = 11; // maxdepth + extra_doublings the kernel is laid out for (sums, pend table); the engine checks
+// (LOCK_MAXDEPTH, the maxdepth + extra_doublings the sums and the pend table below are laid out for: nuts_contract.hpp)
 constexpr int MAX_GROUPS = LOCK_MAXDEPTH + 1;
 constexpr int NSUM = 8 + 6 * MAX_GROUPS;
 constexpr int NUNIT = 4;           // momentum-refresh units (wavefronts 4 .. 4 + NUNIT - 1)

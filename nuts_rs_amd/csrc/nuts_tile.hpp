@@ -29,33 +29,17 @@
 #ifndef NM_LDS_L1
 #define NM_LDS_L1 0          // the per-chain LDS of 16 resident chains must leave room for the column tiles
 #endif
+#include "nuts_contract.hpp"
 #include "nuts_kernels.hpp"
 
 namespace nm {
 namespace tile {
 
-#ifndef NM_TILE_CHAINS
-#define NM_TILE_CHAINS 16    // chains = wavefronts per block: 16 (all 16 columns of the f64 MFMA carry a chain) or 8 (half of them; tuning builds)
-#endif
-#ifndef NM_TILE_OCC
-#define NM_TILE_OCC 1        // blocks per compute unit the register allocation leaves room for
-#endif
+// (NM_TILE_CHAINS, NM_TILE_OCC and TileMats, the shared matrices in MFMA operand order: nuts_contract.hpp — the engine fills them)
 constexpr int TC = NM_TILE_CHAINS;  // chains = wavefronts per block
 static_assert(TC == 16 || TC == 8, "a column tile holds 16 or 8 chains");
 constexpr int TD = 256;             // rows of a column tile: dim and rank <= 256
 typedef double v4d __attribute__((ext_vector_type(4)));
-
-// The shared matrices in MFMA operand order.  For a product out[R x 16] = M[R x K] B[K x 16], stripe s (rows 16 s ..),
-// k-pair q (inner indices 8 q .. 8 q + 7): packed[(s * kpairs + q) * 64 + lane] = { M[16 s + (lane & 15)][8 q + (lane >> 4)],
-// M[16 s + (lane & 15)][8 q + 4 + (lane >> 4)] } — two A operands per 16-byte load, 1 KiB per wave instruction.
-struct TileMats {
-    const double* ut;        // M = U'  (rank x dim):  M[k][d] = vecs[k][d]
-    const double* u;         // M = U   (dim x rank):  M[d][k] = vecs[k][d]
-    const double* p;         // M[d][j] = P[j][d]      (the one-chain density's column order)
-    int dim, rank;
-    int dim_kp, rank_kp;     // k-pairs of inner length dim / rank (padded with zeros)
-    int dim_st, rank_st;     // 16-row stripes of dim / rank outputs
-};
 
 struct alignas(16) TileShared {
     double zin[TD * TC];     // the chains' input columns; the second product of an apply accumulates in place

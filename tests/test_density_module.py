@@ -25,7 +25,7 @@ def module_path(dim=DIM):
 
 def ensure_module(dim=DIM, group=False, lane=False):
     out = module_path(dim) if not (group or lane) else os.path.join(MODDIR, f"my_diag_normal_{'lane' if lane else 'group'}_dim{dim}.so")
-    srcs = [HEADER] + [os.path.join(B.CSRC, f) for f in ("density_module.hip", "nuts_kernels.hpp", "nuts_launch.hpp", "dev_math.hpp",
+    srcs = [HEADER] + [os.path.join(B.CSRC, f) for f in ("density_module.hip", "nuts_contract.hpp", "nuts_kernels.hpp", "nuts_launch.hpp", "dev_math.hpp",
                                                           "nuts_group.hpp", "nuts_group_impl.hpp", "nuts_lane.hpp", "nuts_adapt.hpp")]
     srcs.append(os.path.join(HERE, "..", "include", "nuts_amd.h"))       # the ABI version is part of the module
     if not os.path.exists(out) or any(os.path.getmtime(s) > os.path.getmtime(out) for s in srcs):
@@ -137,7 +137,7 @@ def test_user_density_lane_form_matches_oracle(oracle):
 
 def ensure_variant_module(dim=DIM):
     out = os.path.join(MODDIR, f"my_diag_normal_variants_dim{dim}.so")
-    srcs = [HEADER] + [os.path.join(B.CSRC, f) for f in ("density_module.hip", "nuts_kernels.hpp", "nuts_launch.hpp", "dev_math.hpp")]
+    srcs = [HEADER] + [os.path.join(B.CSRC, f) for f in ("density_module.hip", "nuts_contract.hpp", "nuts_kernels.hpp", "nuts_launch.hpp", "dev_math.hpp")]
     srcs.append(os.path.join(HERE, "..", "include", "nuts_amd.h"))
     if not os.path.exists(out) or any(os.path.getmtime(s) > os.path.getmtime(out) for s in srcs):
         os.makedirs(MODDIR, exist_ok=True)
@@ -197,7 +197,7 @@ def test_user_density_with_low_rank_adaptation_trajectory_kinds_and_mclmc(oracle
 
 def ensure_group_variant_module():
     out = os.path.join(MODDIR, f"my_diag_normal_group_kinetic_dim{GROUP_DIM}.so")
-    srcs = [HEADER] + [os.path.join(B.CSRC, f) for f in ("density_module.hip", "nuts_kernels.hpp", "nuts_launch.hpp", "dev_math.hpp", "nuts_group.hpp", "nuts_group_impl.hpp", "nuts_adapt.hpp")]
+    srcs = [HEADER] + [os.path.join(B.CSRC, f) for f in ("density_module.hip", "nuts_contract.hpp", "nuts_kernels.hpp", "nuts_launch.hpp", "dev_math.hpp", "nuts_group.hpp", "nuts_group_impl.hpp", "nuts_adapt.hpp")]
     srcs.append(os.path.join(HERE, "..", "include", "nuts_amd.h"))
     if not os.path.exists(out) or any(os.path.getmtime(s) > os.path.getmtime(out) for s in srcs):
         os.makedirs(MODDIR, exist_ok=True)
@@ -239,7 +239,7 @@ WALLED = os.path.join(HERE, "user_density", "my_walled_normal.hpp")
 def ensure_walled(dim):
     dpl, w = B.pick_tiling(dim)
     out = os.path.join(MODDIR, f"my_walled_normal_dpl{dpl}_w{w}.so")
-    srcs = [WALLED] + [os.path.join(B.CSRC, f) for f in ("density_module.hip", "nuts_kernels.hpp", "nuts_launch.hpp", "dev_math.hpp")]
+    srcs = [WALLED] + [os.path.join(B.CSRC, f) for f in ("density_module.hip", "nuts_contract.hpp", "nuts_kernels.hpp", "nuts_launch.hpp", "dev_math.hpp")]
     srcs.append(os.path.join(HERE, "..", "include", "nuts_amd.h"))
     if not os.path.exists(out) or any(os.path.getmtime(s) > os.path.getmtime(out) for s in srcs):
         os.makedirs(MODDIR, exist_ok=True)

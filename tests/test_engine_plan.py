@@ -17,7 +17,7 @@ CSRC = os.path.join(ROOT, "nuts_rs_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
-@pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="hipcc compiles the host harness (it includes the kernel headers for their constants)")
+@pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="hipcc compiles the host harness (engine_plan.hpp includes dev_math.hpp for its host / device logarithm)")
 def test_engine_plan_matches_the_documented_selection():
     deps = [SRC, os.path.join(ROOT, "include", "nuts_amd.h")] + [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp")]
     if not os.path.exists(EXE) or any(os.path.getmtime(d) > os.path.getmtime(EXE) for d in deps):

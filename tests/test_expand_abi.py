@@ -24,7 +24,7 @@ def ensure_module(header, struct, dim):
     dpl, w = B.pick_tiling(dim)
     out = os.path.join(MODDIR, f"expand_{struct}_dpl{dpl}_w{w}.so")
     srcs = [header, PLAIN_HEADER, os.path.join(HERE, "..", "include", "nuts_amd.h")]
-    srcs += [os.path.join(B.CSRC, f) for f in ("density_module.hip", "nuts_expand.hpp", "nuts_kernels.hpp", "nuts_launch.hpp", "dev_math.hpp",
+    srcs += [os.path.join(B.CSRC, f) for f in ("density_module.hip", "nuts_expand.hpp", "nuts_contract.hpp", "nuts_kernels.hpp", "nuts_launch.hpp", "dev_math.hpp",
                                                "nuts_group.hpp", "nuts_group_impl.hpp", "nuts_adapt.hpp")]
     if not os.path.exists(out) or any(os.path.getmtime(s) > os.path.getmtime(out) for s in srcs):
         os.makedirs(MODDIR, exist_ok=True)

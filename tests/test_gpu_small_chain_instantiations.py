@@ -22,7 +22,7 @@ from helpers import assert_bit_exact, run_engine, run_oracle
 pytestmark = pytest.mark.gpu
 
 # ---- the case list: plain data ---------------------------------------------------------------------------------------------------------------
-# lanes per chain -> (first, last) dim it serves (csrc/nuts_group.hpp group_size), lane pairs -> dims (csrc/nuts_lane.hpp lane_pairs)
+# lanes per chain -> (first, last) dim it serves (csrc/nuts_contract.hpp group_size), lane pairs -> dims (csrc/nuts_contract.hpp lane_pairs)
 GROUP_DIMS = {8: (1, 16), 16: (17, 32), 32: (33, 64)}
 LANE_DIMS = {2: (1, 4), 4: (5, 8), 5: (9, 10)}
 GROUP_FAMILIES = ("euclid", "exact", "micro", "mclmc")     # MCLMC and the kinds are run-time paths of ONE KinWrap instantiation: a run each

@@ -4,8 +4,8 @@ import test_gpu_small_chain_instantiations as M
 
 DENS_GROUP = {"iid": (8, 16, 32), "diag": (8, 16, 32), "funnel": (8, 16, 32), "mvn": (8, 16, 32), "schools": (8,)}
 DENS_LANE = {"iid": (2, 4, 5), "diag": (2, 4, 5), "funnel": (2, 4, 5), "schools": (5,)}
-GROUP_ENDS = {8: (1, 16), 16: (17, 32), 32: (33, 64)}       # csrc/nuts_group.hpp group_size: dim <= 16 / 32 / 64
-LANE_ENDS = {2: (1, 4), 4: (5, 8), 5: (9, 10)}              # csrc/nuts_lane.hpp lane_pairs: dim <= 4 / 8 / 10
+GROUP_ENDS = {8: (1, 16), 16: (17, 32), 32: (33, 64)}       # csrc/nuts_contract.hpp group_size: dim <= 16 / 32 / 64
+LANE_ENDS = {2: (1, 4), 4: (5, 8), 5: (9, 10)}              # csrc/nuts_contract.hpp lane_pairs: dim <= 4 / 8 / 10
 
 
 def _bottom(dens, fam, lo):
@@ -16,8 +16,7 @@ def test_size_functions_match_the_sources():
     import os
     import re
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "nuts_rs_amd", "csrc")
-    g = open(os.path.join(csrc, "nuts_group.hpp")).read()
-    l = open(os.path.join(csrc, "nuts_lane.hpp")).read()
+    g = l = open(os.path.join(csrc, "nuts_contract.hpp")).read()      # (the size rules of both families: what the host shares with the kernels)
     assert re.search(r"group_size\(uint64_t dim\) \{ return dim <= 16 \? 8 : dim <= 32 \? 16 : dim <= 64 \? 32 : 0; \}", g)
     assert re.search(r"lane_pairs\(uint64_t dim\) \{ return dim <= 4 \? 2 : dim <= 8 \? 4 : dim <= 10 \? 5 : 0; \}", l)
     assert [M.group_size(d) for d in (1, 16, 17, 32, 33, 64, 65)] == [8, 8, 16, 16, 32, 32, 0]
