@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define NM_ABI_VERSION 19
+#define NM_ABI_VERSION 20
 
 typedef enum nm_status {
     NM_OK = 0,
@@ -683,6 +683,39 @@ nm_status nm_pooled_partials(uint64_t n_rows, uint64_t dim, const double* d_posi
 nm_status nm_pooled_exchange(void* rccl_comm, uint64_t world, uint64_t dim, const double* d_payload, double* d_gathered, void* stream);
 nm_status nm_pooled_finish(uint64_t world, uint64_t dim, const double* d_gathered, double* d_sigma, double* d_mean, double* d_count, void* stream);
 const char* nm_pooled_last_error(void);
+
+/* ---------------------------------------------------------------------------------------------
+ * The centred scatter matrix of a window of rows (ABI v20): S = sum over the kept rows of (x - c)(x - c)', dim x dim, on the f64
+ * matrix cores.  It is what a pooled LOW-RANK estimate needs of a window (nuts_rs_amd/pooled.py: the reference's estimate,
+ * src/transform/adapt/low_rank.rs:73-262, depends on the window only through its count, means and the two scatter matrices of
+ * draws and gradients), and the covariance of a recorded trace falls out of the same call.  NO reference counterpart: defined by
+ * THIS repository, DESIGN §29.  Engine-free, in the family of nm_pooled_partials.
+ *
+ * Input: d_rows[n_rows][dim], f64, row-major; d_center[dim]; d_stats NULL or the rows' nm_draw_stats (same row order).
+ * A row is KEPT under exactly the rule of nm_pooled_partials (no statistics: every row; else the chain is healthy and the draw is
+ * one the reference's collector keeps).  A row that is left out contributes nothing: it is selected away, never multiplied by
+ * zero (rows of failed chains hold NaN).  A kept row r gives y_r[d] = x_r[d] - c[d], ONE rounded binary64 subtraction.
+ * Slabs: the rows are cut by n_rows alone — not by dim, not by the grid:
+ *   n_slabs = clamp(ceil(n_rows / NM_SCATTER_SLAB_MIN_ROWS), 1, NM_SCATTER_MAX_SLABS);   R = 4 * ceil(ceil(n_rows / n_slabs) / 4);
+ *   slab s = rows [s R, min((s + 1) R, n_rows))   (a trailing slab may be empty).
+ * Per slab s and output (i, j): acc = +0.0; for r ascending over the slab's kept rows: acc = fma(y_r[i], y_r[j], acc) — ONE fused
+ * multiply-add per row, one accumulator per output and slab (v_mfma_f64_16x16x4_f64 is this chain, k ascending: DESIGN §10).
+ * S[i][j] = the slab values added in slab order from +0.0 with plain binary64 additions.  S is written FULL, [dim][dim], and is
+ * exactly symmetric (fma(a, b, c) == fma(b, a, c)).  *d_count (nullable) = the number of kept rows, as a double.
+ * A NaN or an infinity in a kept row reaches row and column of its element only (and what IEEE arithmetic makes of it there).
+ * The bits do not depend on the grid, on the alignment of d_rows or on what else runs on the device; tests/scatter_ref.py restates
+ * the definition on the host with the same bits.
+ *
+ * Asynchronous on `stream`.  The rows are read T = ceil(dim / 64) times (once for dim <= 64), no copy of them is made.  Scratch (stream-ordered,
+ * freed behind the kernels): n_slabs x T (T + 1) / 2 x 4096 + n_slabs doubles.
+ * NM_ERR_INVALID_ARG — decided before any device call — for: a null d_rows / d_center / d_scatter; n_rows == 0; dim == 0;
+ * dim > NM_SCATTER_MAX_DIM.  The message of a failure is nm_pooled_last_error's.
+ * ------------------------------------------------------------------------------------------- */
+#define NM_SCATTER_SLAB_MIN_ROWS 256
+#define NM_SCATTER_MAX_SLABS 64
+#define NM_SCATTER_MAX_DIM 1024
+nm_status nm_pooled_scatter(uint64_t n_rows, uint64_t dim, const double* d_rows, const double* d_center,
+                            const nm_draw_stats* d_stats, double* d_scatter, double* d_count, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Posterior summaries of a recorded trace, computed where the trace lies: per element the mean, the standard deviation, the

@@ -340,6 +340,15 @@ inline void quantile_draws(const double* d_draws, uint64_t n_draws, uint64_t n_c
     if (st != NM_OK) throw NutsError(st, nm_quantile_last_error());
 }
 
+// The centred scatter matrix S = sum (x - c)(x - c)' of rows that lie on the device (nm_pooled_scatter; defined in nuts_amd.h): d_rows
+// [n_rows][dim], d_center [dim], d_scatter [dim][dim] written full and symmetric; d_stats (the rows' statistics: only the rows the pooled
+// adaptation keeps count) and d_count (the number of kept rows) may be null.  Asynchronous on `stream`.
+inline void pooled_scatter(const double* d_rows, uint64_t n_rows, uint64_t dim, const double* d_center, double* d_scatter,
+                           const nm_draw_stats* d_stats = nullptr, double* d_count = nullptr, void* stream = nullptr) {
+    const nm_status st = nm_pooled_scatter(n_rows, dim, d_rows, d_center, d_stats, d_scatter, d_count, stream);
+    if (st != NM_OK) throw NutsError(st, nm_pooled_last_error());
+}
+
 struct ChainProgress {             // src/sampler.rs:1009-1051
     uint64_t finished_draws = 0, total_draws = 0, divergences = 0;
     bool tuning = true, started = false;

@@ -29,7 +29,7 @@ ABI_SYMBOLS = [
     "nm_pick_tiling", "nm_probe_bandwidth", "nm_probe_issue", "nm_settings_default_low_rank", "nm_settings_default_mclmc", "nm_engine_set_lowrank_estimator",
     "nm_lowrank_compute_update", "nm_lowrank_test_spd_mean", "nm_lowrank_test_estimate_mass_matrix", "nm_engine_set_lowrank_estimator_place", "nm_engine_lowrank_device_updates", "nm_lowrank_block_twin", "nm_lowrank_test_block_device", "nm_engine_set_transform", "nm_engine_get_lowrank", "nm_engine_lowrank_max_rank",
     "nm_lowrank_transform_batch", "nm_engine_set_positions_masked", "nm_engine_init_positions_retry",
-    "nm_init_positions_uniform_at", "nm_engine_tile_launches", "nm_engine_lockstep_launches", "nm_engine_reduce_order", "nm_engine_host_logp_calls", "nm_pooled_partials", "nm_pooled_exchange", "nm_pooled_finish", "nm_pooled_last_error",
+    "nm_init_positions_uniform_at", "nm_engine_tile_launches", "nm_engine_lockstep_launches", "nm_engine_reduce_order", "nm_engine_host_logp_calls", "nm_pooled_partials", "nm_pooled_exchange", "nm_pooled_finish", "nm_pooled_last_error", "nm_pooled_scatter",
     "nm_logp_expanded_dim", "nm_engine_expanded_dim", "nm_engine_expand", "nm_summarize_draws", "nm_summary_last_error",
     "nm_quantile_draws", "nm_quantile_last_error",
     # the per-vector `Math` seam
@@ -113,6 +113,10 @@ class NmSummaryOutputs(C.Structure):
 
 
 NM_QUANTILE_MAX_PROBS = 16
+# nm_pooled_scatter: how the rows are cut into slabs, and the widest matrix (include/nuts_amd.h)
+NM_SCATTER_SLAB_MIN_ROWS = 256
+NM_SCATTER_MAX_SLABS = 64
+NM_SCATTER_MAX_DIM = 1024
 
 
 class NmQuantileSpec(C.Structure):
@@ -290,6 +294,7 @@ def load():
     L.nm_pooled_exchange.argtypes = [vp, u64, u64, vp, vp, vp]
     L.nm_pooled_finish.argtypes = [u64, u64, vp, vp, vp, vp, vp]
     L.nm_pooled_last_error.restype = C.c_char_p
+    L.nm_pooled_scatter.argtypes = [u64, u64, vp, vp, vp, vp, vp, vp]
     L.nm_summarize_draws.argtypes = [C.POINTER(NmSummarySpec), vp, C.POINTER(NmSummaryOutputs), vp]
     L.nm_summary_last_error.restype = C.c_char_p
     L.nm_quantile_draws.argtypes = [C.POINTER(NmQuantileSpec), vp, C.POINTER(NmQuantileOutputs), vp]

@@ -13,17 +13,11 @@
 #include <cstdint>
 #include <string>
 #include "../../include/nuts_amd.h"
+#include "pooled_rows.hpp"
 
 namespace {
 constexpr int CHUNK_ROWS = 512;
-
-__device__ inline bool row_ok(const nm_draw_stats* st, uint64_t row) {
-    if (!st) return true;
-    const nm_draw_stats& s = st[row];
-    if (s.chain_status != NM_CHAIN_OK) return false;
-    const int64_t idx = s.index_in_trajectory;
-    return s.diverging ? ((idx < 0 ? -idx : idx) > 4) : (idx != 0);
-}
+using nm::pooled::row_ok;          // (the rule by which a row counts: pooled_rows.hpp, shared with pooled_scatter.hip)
 
 // grid (chunks, ceil(dim / 128), 2): z = 0 draws, 1 gradients.  partial[(z * chunks + chunk) * (1 + 2 dim)] = count, mean, M2
 __global__ __launch_bounds__(128) void pooled_chunk_kernel(uint64_t n_rows, uint64_t dim, const double* x, const double* g,
@@ -112,6 +106,7 @@ all_gather_fn rccl_all_gather() {
 }
 thread_local std::string g_perr;
 }  // namespace
+void nm::pooled::set_error(const std::string& msg) { g_perr = msg; }
 
 extern "C" nm_status nm_pooled_exchange(void* rccl_comm, uint64_t world, uint64_t dim, const double* d_payload, double* d_gathered, void* stream) {
     if (!d_payload || !d_gathered || dim == 0 || world == 0) { g_perr = "nm_pooled_exchange: null argument"; return NM_ERR_INVALID_ARG; }

@@ -586,6 +586,10 @@ class ChainBatch:
         place = {"auto": 0, "host": 1, "device": 2}.get(place, place)
         check(_lib.load().nm_engine_set_lowrank_estimator_place(self._h, int(place)))
 
+    def lowrank_max_rank(self):
+        """The most eigenvectors a transformation of this batch may have (nm_engine_lowrank_max_rank; 0 without the low-rank adaptation)."""
+        return int(_lib.load().nm_engine_lowrank_max_rank(self._h))
+
     def lowrank_device_updates(self):
         """Estimator calls that ran on the device so far."""
         return int(_lib.load().nm_engine_lowrank_device_updates(self._h))
