@@ -741,7 +741,7 @@ nm_status nm_pooled_scatter(uint64_t n_rows, uint64_t dim, const double* d_rows,
  * 2T + 1 <= L: stop at the first P_T that is not > 0, else P = min(P_T, prev), prev = P, tau += 2 P.   ess = (M * n) / tau.
  * ess_truncated = 1 when the loop ran out of lags without meeting a non-positive pair: the reported ESS is then an over-estimate
  * (the caller asked for too few lags).  There is no log10 cap on the ESS.  A constant column gives the NaN that IEEE arithmetic
- * gives (0 / 0 in rhat and rho).  Quantiles are nm_quantile_draws (below); rank-normalisation and nested R-hat are OUT OF SCOPE.
+ * gives (0 / 0 in rhat and rho).  Quantiles are nm_quantile_draws, rank-normalisation is nm_transform_draws (both below); nested R-hat is OUT OF SCOPE.
  *
  * Outputs: device pointers, any may be NULL.  d_mean = gm, d_within_var = W, d_autocorr = rho [L+1][dim], d_chain_mean /
  * d_chain_var = mean_m / var_m [M][dim].  Asynchronous on `stream` when h_chain_ids is NULL; WITH chain ids the call uploads them and
@@ -834,6 +834,84 @@ typedef struct nm_quantile_outputs {         /* device pointers, either may be N
 } nm_quantile_outputs;
 nm_status nm_quantile_draws(const nm_quantile_spec* spec, const double* d_draws, const nm_quantile_outputs* out, void* stream);
 const char* nm_quantile_last_error(void);
+
+/* ---------------------------------------------------------------------------------------------
+ * Rank transforms of a recorded trace: the primitive under rank-normalised R-hat and bulk / tail ESS (Vehtari et al. 2021),
+ * computed where the trace lies.  NO reference counterpart: defined by THIS repository, DESIGN §30.  Engine-free, a post-pass like
+ * nm_summarize_draws, whose input its output is.  PURELY ADDITIVE to ABI v20: new symbols and new structures only, no existing
+ * layout or behaviour is touched, so NM_ABI_VERSION stays 20.
+ *
+ * Input: d_draws[n_draws][n_chains][dim], f64, row-major.  h_chain_ids (host, strictly increasing, < n_chains) selects C' =
+ * n_chain_ids chains; NULL = all chains (C' = n_chains).  The outputs are COMPACT over the selected chains, [n_draws][C'][dim]:
+ * they feed nm_summarize_draws without chain ids.
+ * Pool rows: all N = n_draws rows; with split = 1 and odd N the row N / 2 (rounded down) is left out — it belongs to neither split
+ * series of nm_summarize_draws.  n = pool rows x C'.  A row outside the pool gets d_out = NaN and d_rank2 = 0.
+ * kind:
+ *   NM_TRANSFORM_RANK_NORMAL         v = x; d_param is ignored.
+ *   NM_TRANSFORM_FOLDED_RANK_NORMAL  v = |x - d_param[d]|: one binary64 subtraction, then the sign bit is cleared.
+ *   NM_TRANSFORM_INDICATOR_LE        out = (x <= d_param[d]) ? 1.0 : 0.0 by IEEE comparison; a NaN x gives NaN and is counted in
+ *                                    d_nan_count; a NaN parameter gives NaN for the whole column; there is no pooling: every row is
+ *                                    written, whatever `split`; d_rank2 must be NULL.
+ * The two rank kinds, per element d over the pool's values v:
+ *   key(v) is nm_quantile_draws' key: -inf < ... < -0.0 < +0.0 < ... < +inf.  -0.0 and +0.0 are DISTINCT keys — a stated departure
+ *     from scipy.stats.rankdata, which ties them.
+ *   a = the number of pool keys < key(v), b = the number <= key(v);  rank2 = a + b + 1: twice the 1-based average rank, an integer
+ *     in 2 .. 2n;  out = score(n, rank2).
+ *   A column with any NaN among the pool's v gives NaN in every d_out and 0 in every d_rank2 of that column; d_nan_count[d] is the
+ *     number of NaNs among the pool's v.
+ * score(n, rank2) = Phi^-1((r - 3/8) / (n + 1/4)), r = rank2 / 2, by Wichura's AS241 (PPND16) — every step ONE binary64 operation,
+ * every polynomial a degree-7 Horner evaluation from the top coefficient (coefficients: csrc/rank_score.hpp, AS241's), dlog the
+ * engine's deterministic logarithm:
+ *   A = 4 rank2 - 3;  B = 8 n + 2 (uint64_t);  q = (double)(int64_t)(2 A - B) / (double)(2 B);
+ *   |q| <= 0.425:  r = 0.180625 - q * q;  z = q * Pa(r) / Pb(r);
+ *   otherwise:     t = (double)min(A, B - A) / (double)B;  r = sqrt(-dlog(t));
+ *                  r <= 5: r -= 1.6, w = Pc(r) / Pd(r);  else r -= 5, w = Pe(r) / Pf(r);   z = q < 0 ? -w : w.
+ * It is exactly antisymmetric — score(n, 2n + 2 - rank2) == -score(n, rank2) — and score(n, n + 1) == +0.0.
+ * nm_rank_normal_score is the same function on the host (one header compiled for both sides, no device needed): *z = score(n,
+ * rank2); NM_ERR_INVALID_ARG for n == 0, n > 2^31 - 1, rank2 < 2, rank2 > 2n, a null z.
+ * The ranks come from a segmented least-significant-digit radix sort of (key, pool index) pairs per column (8 passes of 8 bits,
+ * blocks own slabs of NM_RANK_SLAB_KEYS consecutive positions); every number that decides anything is an integer count, so the
+ * bits depend neither on the grid nor on the column batching nor on the order in which blocks arrive; tests/rank_ref.py restates
+ * the definition in numpy with the same bits.
+ *
+ * Outputs: device pointers; d_out[n_draws][C'][dim], d_rank2 uint32_t[n_draws][C'][dim], d_nan_count uint64_t[dim]; d_out or
+ * d_rank2 must be given.  Asynchronous on `stream` when h_chain_ids is NULL; WITH chain ids the call uploads them and waits for
+ * `stream` (hipStreamSynchronize) before it returns, as nm_summarize_draws does.
+ * Scratch (stream-ordered, freed behind the kernels), rank kinds only: per column of a batch 24 n + 1024 ceil(n / NM_RANK_SLAB_KEYS)
+ * bytes (two buffers of key + index, the count table); the columns of a batch are as many as fit into max_scratch_bytes (0 = the
+ * default, 1 GiB), never fewer than one; plus 4 dim bytes of NaN counts and the chain ids, outside that budget.
+ * NM_ERR_INVALID_ARG — decided before any device call — for: a null spec / draws / outputs; d_out and d_rank2 both NULL; d_param
+ * NULL for kinds 1 and 2; d_rank2 given for kind 2; an unknown kind; split > 1; dim, n_chains or n_draws == 0; n == 0; n above
+ * 2^31 - 1 (rank2 is 32-bit and 2 B stays exact in a double); dim above 2^31 - 1; chain ids not strictly increasing or out of
+ * range (n_chain_ids == 0 with ids given); d_out overlapping d_draws.
+ * h_chain_ids, d_rank2 and d_nan_count are void* for the reason given at nm_summary_spec.  nm_transform_last_error: the message of
+ * this call's last failure on the calling thread.
+ * ------------------------------------------------------------------------------------------- */
+#define NM_RANK_SLAB_KEYS 8192
+#define NM_TRANSFORM_RANK_NORMAL 0
+#define NM_TRANSFORM_FOLDED_RANK_NORMAL 1
+#define NM_TRANSFORM_INDICATOR_LE 2
+typedef struct nm_transform_spec {
+    uint64_t n_draws;
+    uint64_t n_chains;
+    uint64_t dim;
+    uint64_t kind;                 /* NM_TRANSFORM_* */
+    uint64_t split;                /* 0 / 1 */
+    uint64_t n_chain_ids;          /* ignored when h_chain_ids is NULL */
+    void* h_chain_ids;             /* const uint64_t[n_chain_ids] on the host, only read; NULL = all chains */
+    uint64_t max_scratch_bytes;    /* 0 = 1 GiB */
+    uint64_t reserved[2];
+} nm_transform_spec;
+typedef struct nm_transform_outputs {        /* device pointers */
+    double* d_out;           /* [n_draws][C'][dim] */
+    void* d_rank2;           /* uint32_t[n_draws][C'][dim], may be NULL */
+    void* d_nan_count;       /* uint64_t[dim], may be NULL */
+    uint64_t reserved[2];
+} nm_transform_outputs;
+nm_status nm_transform_draws(const nm_transform_spec* spec, const double* d_draws, const double* d_param,
+                             const nm_transform_outputs* out, void* stream);
+const char* nm_transform_last_error(void);
+nm_status nm_rank_normal_score(uint64_t n, uint64_t rank2, double* z);
 
 const char* nm_last_error(void);
 uint64_t    nm_abi_version(void);

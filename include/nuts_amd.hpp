@@ -340,6 +340,21 @@ inline void quantile_draws(const double* d_draws, uint64_t n_draws, uint64_t n_c
     if (st != NM_OK) throw NutsError(st, nm_quantile_last_error());
 }
 
+// The rank transforms of a trace that lies on the device (nm_transform_draws; defined in nuts_amd.h): kind NM_TRANSFORM_RANK_NORMAL the
+// normal scores of the pooled ranks per element, NM_TRANSFORM_FOLDED_RANK_NORMAL those of |x - d_param[d]|, NM_TRANSFORM_INDICATOR_LE
+// x <= d_param[d].  out.d_out is [n_draws][selected chains][dim] — compact, it feeds summarize_draws without chain ids —, out.d_rank2
+// uint32_t of the same shape, out.d_nan_count uint64_t[dim].  Asynchronous on `stream` unless chain_ids is given.
+inline void transform_draws(const double* d_draws, uint64_t n_draws, uint64_t n_chains, uint64_t dim, uint64_t kind, const double* d_param,
+                            const nm_transform_outputs& out, bool split = true, const std::vector<uint64_t>* chain_ids = nullptr,
+                            uint64_t max_scratch_bytes = 0, void* stream = nullptr) {
+    nm_transform_spec spec{};
+    spec.n_draws = n_draws; spec.n_chains = n_chains; spec.dim = dim; spec.kind = kind; spec.split = split ? 1 : 0;
+    spec.max_scratch_bytes = max_scratch_bytes;
+    if (chain_ids) { spec.n_chain_ids = chain_ids->size(); spec.h_chain_ids = const_cast<uint64_t*>(chain_ids->data()); }
+    const nm_status st = nm_transform_draws(&spec, d_draws, d_param, &out, stream);
+    if (st != NM_OK) throw NutsError(st, nm_transform_last_error());
+}
+
 // The centred scatter matrix S = sum (x - c)(x - c)' of rows that lie on the device (nm_pooled_scatter; defined in nuts_amd.h): d_rows
 // [n_rows][dim], d_center [dim], d_scatter [dim][dim] written full and symmetric; d_stats (the rows' statistics: only the rows the pooled
 // adaptation keeps count) and d_count (the number of kept rows) may be null.  Asynchronous on `stream`.

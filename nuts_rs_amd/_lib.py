@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "nm_lowrank_transform_batch", "nm_engine_set_positions_masked", "nm_engine_init_positions_retry",
     "nm_init_positions_uniform_at", "nm_engine_tile_launches", "nm_engine_lockstep_launches", "nm_engine_reduce_order", "nm_engine_host_logp_calls", "nm_pooled_partials", "nm_pooled_exchange", "nm_pooled_finish", "nm_pooled_last_error", "nm_pooled_scatter",
     "nm_logp_expanded_dim", "nm_engine_expanded_dim", "nm_engine_expand", "nm_summarize_draws", "nm_summary_last_error",
-    "nm_quantile_draws", "nm_quantile_last_error",
+    "nm_quantile_draws", "nm_quantile_last_error", "nm_transform_draws", "nm_transform_last_error", "nm_rank_normal_score",
     # the per-vector `Math` seam
     "nm_math_create", "nm_math_destroy", "nm_math_dim", "nm_math_threads", "nm_math_last_error", "nm_vec_new", "nm_vec_free", "nm_vec_read_from_slice", "nm_vec_write_to_slice", "nm_vec_copy_into", "nm_vec_fill_array", "nm_vec_array_recip", "nm_vec_axpy_out", "nm_vec_axpy", "nm_vec_array_mult", "nm_vec_array_vector_dot", "nm_vec_scalar_prods3", "nm_vec_array_gaussian", "nm_vec_array_update_variance", "nm_vec_array_update_var_inv_std_draw_grad", "nm_vec_array_update_var_inv_std_grad", "nm_vec_array_update_var_inv_std_draw", "nm_vec_array_sum_ln", "nm_vec_array_all_finite", "nm_vec_logp_array", "nm_vec_sq_norm_sum", "nm_vec_std_norm_flow", "nm_vec_std_norm_grad_flow", "nm_vec_esh_momentum_update", "nm_vec_array_normalize",
 ]
@@ -126,6 +126,20 @@ class NmQuantileSpec(C.Structure):
 
 class NmQuantileOutputs(C.Structure):
     _fields_ = [("d_quantiles", C.c_void_p), ("d_nan_count", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+# nm_transform_draws: the kinds, and the positions of a column a block of the sort owns (include/nuts_amd.h)
+NM_RANK_SLAB_KEYS = 8192
+NM_TRANSFORM_RANK_NORMAL, NM_TRANSFORM_FOLDED_RANK_NORMAL, NM_TRANSFORM_INDICATOR_LE = 0, 1, 2
+
+
+class NmTransformSpec(C.Structure):
+    _fields_ = [("n_draws", C.c_uint64), ("n_chains", C.c_uint64), ("dim", C.c_uint64), ("kind", C.c_uint64), ("split", C.c_uint64),
+                ("n_chain_ids", C.c_uint64), ("h_chain_ids", C.c_void_p), ("max_scratch_bytes", C.c_uint64), ("reserved", C.c_uint64 * 2)]
+
+
+class NmTransformOutputs(C.Structure):
+    _fields_ = [("d_out", C.c_void_p), ("d_rank2", C.c_void_p), ("d_nan_count", C.c_void_p), ("reserved", C.c_uint64 * 2)]
 
 
 # nm_lowrank_estimator_fn
@@ -299,6 +313,9 @@ def load():
     L.nm_summary_last_error.restype = C.c_char_p
     L.nm_quantile_draws.argtypes = [C.POINTER(NmQuantileSpec), vp, C.POINTER(NmQuantileOutputs), vp]
     L.nm_quantile_last_error.restype = C.c_char_p
+    L.nm_transform_draws.argtypes = [C.POINTER(NmTransformSpec), vp, vp, C.POINTER(NmTransformOutputs), vp]
+    L.nm_transform_last_error.restype = C.c_char_p
+    L.nm_rank_normal_score.argtypes = [u64, u64, C.POINTER(dbl)]
     L.nm_last_error.restype = C.c_char_p
     L.nm_abi_version.restype = u64
     for name in ABI_SYMBOLS:

@@ -528,12 +528,15 @@ class ChainBatch:
         self.synchronize()
         return out if is_tensor else out.cpu().numpy()
 
-    def draw_summary(self, n_draws, expanded=False, split=True, max_lag=32, quantiles=None):
+    def draw_summary(self, n_draws, expanded=False, split=True, max_lag=32, quantiles=None, rank_normalized=False):
         """n_draws draws of every chain into device buffers, summarised where they lie (summarize_draws): returns (Summary, stats
         [n_draws, n_chains] on the host).  Chains whose last chain_status is not NM_CHAIN_OK are left out of the summary.
         expanded=True summarises the expanded draws instead of the positions.  No position row crosses PCIe.
         quantiles: a list of probabilities; the Summary then also carries `quantiles` [len(quantiles), dim] (quantile_draws over
-        the same buffers and the same chains) and `quantile_probs`.  None (the default): neither is computed."""
+        the same buffers and the same chains) and `quantile_probs`.  None (the default): neither is computed.
+        rank_normalized=True: the result is a RankSummary, a Summary that also carries rhat_rank, ess_bulk, ess_tail and the two
+        *_truncated flags (rank_diagnostics over the same buffers and the same chains).  False (the default): nothing more is launched,
+        the result is a plain Summary and the five read as None."""
         import torch
         dev = torch.device("cuda", self._device)                # the engine's device, whatever torch's current one is
         pos = torch.empty((n_draws, self.n_chains, self.logp.dim), dtype=torch.float64, device=dev)
@@ -555,6 +558,10 @@ class ChainBatch:
         if quantiles is not None:
             summary.quantile_probs = np.array(quantiles, dtype=np.float64)
             summary.quantiles, _ = quantile_draws(ex if expanded else pos, summary.quantile_probs, chain_ids=ids)
+        if rank_normalized:
+            rd = rank_diagnostics(ex if expanded else pos, split=split, max_lag=max_lag, chain_ids=ids)
+            summary = RankSummary(**{f.name: getattr(summary, f.name) for f in fields(summary)}, rhat_rank=rd.rhat_rank, ess_bulk=rd.ess_bulk,
+                                  ess_tail=rd.ess_tail, ess_bulk_truncated=rd.ess_bulk_truncated, ess_tail_truncated=rd.ess_tail_truncated)
         return summary, stats
 
     # ---- the low-rank transformation (LowRankNutsSettings; reference src/transform/low_rank.rs) ----
@@ -657,6 +664,19 @@ class Summary:
     n_per_series: int
     quantiles: np.ndarray = None          # [n_probs, dim]; only from draw_summary(..., quantiles=[...])
     quantile_probs: np.ndarray = None
+    # the rank-normalised diagnostics are fields of RankSummary (below); a plain Summary keeps its field list and reads them as None
+    rhat_rank = ess_bulk = ess_tail = ess_bulk_truncated = ess_tail_truncated = None
+
+
+@dataclass
+class RankSummary(Summary):
+    """A Summary that also carries the rank-normalised diagnostics (RankDiagnostics' fields of the same names), after the fields of
+    Summary: what draw_summary(..., rank_normalized=True) returns."""
+    rhat_rank: np.ndarray = None
+    ess_bulk: np.ndarray = None
+    ess_tail: np.ndarray = None
+    ess_bulk_truncated: np.ndarray = None
+    ess_tail_truncated: np.ndarray = None
 
 
 def summarize_draws(draws, split=True, max_lag=32, chain_ids=None) -> Summary:
@@ -719,6 +739,97 @@ def quantile_draws(draws, probs, chain_ids=None):
         _lib.check_status(L.nm_quantile_draws(C.byref(spec), C.c_void_p(t.data_ptr() or None), C.byref(out), None), L.nm_quantile_last_error)
         torch.cuda.synchronize(t.device)
     return q.cpu().numpy(), nan.cpu().numpy().astype(np.uint64)
+
+
+def transform_draws(draws, kind, param=None, split=True, chain_ids=None, out=None, ranks=False, max_scratch_bytes=0):
+    """The rank transforms of draws [n_draws, n_chains, dim] (nm_transform_draws, include/nuts_amd.h), computed on the GPU: kind 0 the
+    normal scores of the pooled ranks per element, kind 1 those of |x - param[d]|, kind 2 the indicator x <= param[d].  Returns
+    (out [n_draws, n_selected_chains, dim], rank2 or None, nan_count [dim]): rank2 (uint32, twice the average rank) only with
+    ranks=True.  A float64 CUDA tensor is read where it lies and out / rank2 come back as tensors on its device; anything else goes
+    through numpy and one upload and comes back as arrays.  out: a float64 CUDA tensor of the output's shape to write into (it is
+    returned), or False for no scores (ranks only).  chain_ids: a strictly increasing list of the chains to use (default: all);
+    max_scratch_bytes bounds the sort's scratch (0: 1 GiB), never below one column's."""
+    import torch
+    is_tensor = isinstance(draws, torch.Tensor)
+    t = draws if is_tensor else torch.from_numpy(np.ascontiguousarray(draws, dtype=np.float64))
+    if t.dtype != torch.float64 or t.dim() != 3:
+        raise ValueError("draws must be float64 [n_draws, n_chains, dim]")
+    t = t.contiguous()
+    if not t.is_cuda:
+        t = t.cuda()
+    N, Cn, D = (int(v) for v in t.shape)
+    ids = None if chain_ids is None else np.ascontiguousarray(chain_ids, dtype=np.uint64)
+    csel = Cn if ids is None else len(ids)
+    spec = _lib.NmTransformSpec(N, Cn, D, int(kind), int(bool(split)), 0 if ids is None else len(ids), None if ids is None else ids.ctypes.data,
+                                int(max_scratch_bytes))
+    with torch.cuda.device(t.device):
+        p = None
+        if param is not None:
+            p = param if isinstance(param, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(param, dtype=np.float64))
+            if p.dtype != torch.float64 or tuple(p.shape) != (D,):
+                raise ValueError("param must be float64 [dim]")
+            p = p.contiguous().to(t.device)
+        if out is None:
+            out = torch.empty((N, csel, D), dtype=torch.float64, device=t.device)
+        elif out is not False:
+            if not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (N, csel, D)):
+                raise ValueError(f"out must be a contiguous float64 CUDA tensor of shape {(N, csel, D)}")
+        r2 = torch.empty((N, csel, D), dtype=torch.int32, device=t.device) if ranks else None
+        nan = torch.empty((D,), dtype=torch.int64, device=t.device)
+        o = _lib.NmTransformOutputs((out.data_ptr() or None) if out is not False else None, (r2.data_ptr() or None) if ranks else None, nan.data_ptr() or None)
+        torch.cuda.current_stream(t.device).synchronize()       # the call runs on the null stream: the rows must be there
+        L = _lib.load()
+        _lib.check_status(L.nm_transform_draws(C.byref(spec), C.c_void_p(t.data_ptr() or None), C.c_void_p(p.data_ptr() if p is not None else None),
+                                               C.byref(o), None), L.nm_transform_last_error)
+        torch.cuda.synchronize(t.device)
+    nan_count = nan.cpu().numpy().astype(np.uint64)
+    if out is False:
+        out = None
+    if is_tensor:
+        return out, (r2.view(torch.uint32) if ranks else None), nan_count
+    return (None if out is None else out.cpu().numpy()), (r2.cpu().numpy().view(np.uint32) if ranks else None), nan_count
+
+
+@dataclass
+class RankDiagnostics:
+    """Rank-normalised convergence diagnostics of a trace (Vehtari et al. 2021; rank_diagnostics): arrays over the elements of a draw."""
+    rhat_rank: np.ndarray             # max of the split R-hat of the rank-normalised and of the folded rank-normalised draws
+    ess_bulk: np.ndarray
+    ess_tail: np.ndarray              # min of the ESS of the indicators x <= q05 and x <= q95
+    ess_bulk_truncated: np.ndarray
+    ess_tail_truncated: np.ndarray
+    nan_count: np.ndarray
+
+
+def rank_diagnostics(draws, split=True, max_lag=32, chain_ids=None, max_scratch_bytes=0) -> RankDiagnostics:
+    """Rank-normalised R-hat and bulk / tail ESS per element of draws [n_draws, n_chains, dim], computed on the GPU from calls that exist:
+    quantile_draws for the 5 %, 50 % and 95 % quantiles over all draws, then ONE [n_draws, n_selected_chains, dim] buffer that takes four
+    transforms in turn (transform_draws), each summarised by summarize_draws — the normal scores (bulk ESS, R-hat), the scores folded
+    about the median (R-hat), the indicators of the two tail quantiles (tail ESS).  The ESS is summarize_draws': the caller's max_lag,
+    no FFT, no cap; a *_truncated flag says that it ran out of lags."""
+    import torch
+    t = draws if isinstance(draws, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(draws, dtype=np.float64))
+    if t.dtype != torch.float64 or t.dim() != 3:
+        raise ValueError("draws must be float64 [n_draws, n_chains, dim]")
+    t = t.contiguous()
+    if not t.is_cuda:
+        t = t.cuda()
+    N, Cn, D = (int(v) for v in t.shape)
+    csel = Cn if chain_ids is None else len(chain_ids)
+    q, _ = quantile_draws(t, [0.05, 0.5, 0.95], chain_ids=chain_ids)
+    buf = torch.empty((N, csel, D), dtype=torch.float64, device=t.device)
+    kw = dict(split=split, chain_ids=chain_ids, out=buf, max_scratch_bytes=max_scratch_bytes)
+    _, _, nan_count = transform_draws(t, _lib.NM_TRANSFORM_RANK_NORMAL, **kw)
+    bulk = summarize_draws(buf, split=split, max_lag=max_lag)
+    transform_draws(t, _lib.NM_TRANSFORM_FOLDED_RANK_NORMAL, param=q[1], **kw)
+    folded = summarize_draws(buf, split=split, max_lag=max_lag)
+    transform_draws(t, _lib.NM_TRANSFORM_INDICATOR_LE, param=q[0], **kw)
+    lower = summarize_draws(buf, split=split, max_lag=max_lag)
+    transform_draws(t, _lib.NM_TRANSFORM_INDICATOR_LE, param=q[2], **kw)
+    upper = summarize_draws(buf, split=split, max_lag=max_lag)
+    return RankDiagnostics(rhat_rank=np.maximum(bulk.rhat, folded.rhat), ess_bulk=bulk.ess, ess_tail=np.minimum(lower.ess, upper.ess),
+                           ess_bulk_truncated=bulk.ess_truncated, ess_tail_truncated=lower.ess_truncated | upper.ess_truncated,
+                           nan_count=nan_count)
 
 
 def sample(settings: DiagNutsSettings, logp: LogpSpec, x0=None, chain_id_offset=0, device=-1, chunk_bytes=0, expanded=False):
