@@ -913,6 +913,123 @@ nm_status nm_transform_draws(const nm_transform_spec* spec, const double* d_draw
 const char* nm_transform_last_error(void);
 nm_status nm_rank_normal_score(uint64_t n, uint64_t rank2, double* z);
 
+/* ---------------------------------------------------------------------------------------------
+ * Sampler diagnostics from the recorded draw statistics, computed where the records lie: statistics fields as a trace
+ * (nm_stats_columns) and per-chain / pooled sampler diagnostics with the divergence events (nm_diagnose_stats).  NO reference
+ * counterpart (nutpie leaves this to ArviZ on the host): defined by THIS repository, DESIGN §31.  Engine-free post-passes in the
+ * family of nm_summarize_draws.  PURELY ADDITIVE to ABI v20: new symbols and new structures only, NM_ABI_VERSION stays 20.
+ *
+ * Input of both: d_stats, the nm_draw_stats records as nm_engine_draw_ex leaves them ([n_draws][n_chains], NM_STAT_WORDS 8-byte
+ * words each; the base need only be 8-byte aligned).
+ * WHICH ROWS ARE WRITTEN: a record is UNWRITTEN iff its chain_status word is all ones (0xFFFFFFFFFFFFFFFF).  PRECONDITION: the
+ * engine never writes the rows of a chain that has stopped or never started, so a caller whose chains may stop fills the buffer
+ * with 0xFF bytes before the draw call (ChainBatch.draw_summary does); rows the engine wrote carry an NM_CHAIN_* status.
+ *
+ * nm_stats_columns: d_out[n_rows][n_fields], d_out[r][i] = word h_fields[i] of record r as a double.  With n_rows = n_draws *
+ * n_chains that is [n_draws][n_chains][n_fields]: the input of nm_summarize_draws, nm_quantile_draws and nm_transform_draws with
+ * dim = n_fields (the R-hat and ESS of lp__ and energy).  h_fields[i] is a word index 0 .. NM_STAT_WORDS - 1 (the position of the
+ * member in nm_draw_stats); indices may repeat; 1 <= n_fields <= NM_STAT_WORDS.  They travel in the KERNEL ARGUMENTS: nothing is
+ * uploaded, h_fields is free on return.  Conversion, per word:
+ *   double words (9 step_size .. 18 divergence_energy_error, 22 energy_change, 23 average_step_size): copied bit for bit;
+ *   uint64_t words (0 draw .. 6 n_steps, 19 chain_status, 21 num_eigenvalues): ONE (double)(uint64_t) conversion;
+ *   int64_t words (7 index_in_trajectory, 8 transformation_index, 20 transformation_update_id): ONE (double)(int64_t) conversion;
+ *   every field of an unwritten record: NaN, bits 0x7FF8000000000000.
+ * Each record's bytes are read once, whatever n_fields is.  Asynchronous on `stream`, no scratch.
+ * NM_ERR_INVALID_ARG — decided before any device call — for: a null h_fields / d_stats / d_out; n_rows == 0; n_fields outside
+ * 1 .. NM_STAT_WORDS; a field index >= NM_STAT_WORDS; d_out overlapping d_stats.
+ *
+ * nm_diagnose_stats.  `phase` selects rows: NM_DIAG_ALL every written row, NM_DIAG_SAMPLING those with tuning == 0,
+ * NM_DIAG_TUNING those with tuning != 0.  Per chain c the SELECTED rows are the written rows of the phase, t ascending; k is their
+ * number, kd = (double)k.  Every sum below is serial over the selected rows from 0.0 (integers: from 0), every floating operation
+ * ONE binary64 + - * or / (no fused multiply-add); a floating result that is a NaN is stored as 0x7FF8000000000000.
+ * d_chain_counts[c][NM_DIAG_C_*] (uint64_t):
+ *   ROWS = k;  DIVERGING = rows with diverging != 0;  MAXDEPTH = rows with maxdepth_reached != 0;  LEAPFROGS = sum of n_steps
+ *   modulo 2^64;  MAX_DEPTH = the largest depth, 0 when k = 0;  FINAL_STATUS = the chain_status word of row n_draws - 1 verbatim,
+ *   whatever the phase (all ones: unwritten — the chain stopped or never started).
+ * d_chain_values[c][NM_DIAG_V_*], E_j the energy of the j-th selected row:
+ *   MEAN_ACCEPT = (sum mean_tree_accept) / kd;   ENERGY_MEAN m = (sum E_j) / kd;
+ *   ENERGY_VAR v = (sum (E_j - m) * (E_j - m)) / kd   (ddof 0: ArviZ's bfmi convention);
+ *   BFMI = ((sum_{j >= 1} (E_j - E_{j-1}) * (E_j - E_{j-1})) / (double)(k - 1)) / v, k - 1 in uint64_t arithmetic — the differences
+ *   run over consecutive SELECTED rows;   MEAN_LOGP = (sum logp) / kd;   LAST_STEP_SIZE = step_size of the last selected row, NaN
+ *   when k = 0.   k = 0 and k = 1 give what IEEE arithmetic gives (0 / 0: NaN); non-finite energies propagate.
+ * Pooled, over the HEALTHY chains (FINAL_STATUS == NM_CHAIN_OK).  d_pooled_counts[NM_DIAG_P_*] (uint64_t): HEALTHY chains; ROWS,
+ *   DIVERGING, MAXDEPTH, LEAPFROGS = the sums of the chains' columns (modulo 2^64); CHAINS_DIVERGING = chains with DIVERGING > 0;
+ *   CHAINS_LOW_BFMI = chains with BFMI < bfmi_threshold (false for a NaN); CHAINS_NAN_BFMI = chains whose BFMI is a NaN.
+ *   d_pooled_values[NM_DIAG_PV_*]: MEAN_ACCEPT = S(MEAN_ACCEPT) / (double)HEALTHY, MEAN_STEP_SIZE = S(LAST_STEP_SIZE) /
+ *   (double)HEALTHY, with S the summation pattern of nm_summarize_draws — chunks of NM_SUMMARY_CHUNK_CHAINS consecutive chains,
+ *   inside a chunk serially in c from 0.0 with unhealthy chains SKIPPED (never multiplied by zero), the chunk partials then in
+ *   chunk order from 0.0;  MIN_BFMI = the smallest BFMI of a healthy chain by IEEE <, NaN skipped, +inf when there is none.
+ *   d_depth_hist[b] = the number of selected rows of healthy chains with min(depth, NM_DIAG_DEPTH_BINS - 1) == b.
+ * Events: every selected row with diverging != 0 of ANY chain (healthy or not) is the pair (t, c).  The events come in
+ *   lexicographic (t, c) order; d_events[i] = {t, c} for the first min(n_events, max_events) of them, nothing is written beyond;
+ *   *d_n_events counts ALL events.  The places come from a stable compaction (a bit mask per draw and 64 chains, block counts, a
+ *   scan, placement): no arrival-order cursor.
+ * Integer sums are order-free (atomics add them); every floating number has ONE stated order: the bits depend neither on the grid
+ * nor on the alignment of d_stats nor on what else runs on the device; tests/diag_ref.py restates the definitions in numpy with
+ * the same bits.
+ * Asynchronous on `stream`.  The records are read once; the energies of the selected rows are kept in scratch for the centred sum.
+ * Scratch (stream-ordered, freed behind the kernels): 8 n_draws n_chains bytes of energies, 8 n_draws ceil(n_chains / 64) bytes of
+ * event masks (when events are asked for), 96 n_chains bytes for per-chain outputs that are NULL, and a few hundred words.
+ * NM_ERR_INVALID_ARG — decided before any device call — for: a null spec / d_stats / outputs; every output NULL; n_draws or
+ * n_chains == 0; phase > 2; max_events > 0 with d_events NULL; a NaN bfmi_threshold; n_draws * n_chains above 2^32 - 1.
+ * The integer arrays are void* for the reason given at nm_summary_spec.  nm_diag_last_error: the message of the last failure of
+ * either call on the calling thread.
+ * ------------------------------------------------------------------------------------------- */
+#define NM_STAT_WORDS 24             /* sizeof(nm_draw_stats) / 8 */
+#define NM_DIAG_ALL 0
+#define NM_DIAG_SAMPLING 1
+#define NM_DIAG_TUNING 2
+#define NM_DIAG_CHAIN_COUNTS 6
+#define NM_DIAG_C_ROWS 0
+#define NM_DIAG_C_DIVERGING 1
+#define NM_DIAG_C_MAXDEPTH 2
+#define NM_DIAG_C_LEAPFROGS 3
+#define NM_DIAG_C_MAX_DEPTH 4
+#define NM_DIAG_C_FINAL_STATUS 5
+#define NM_DIAG_CHAIN_VALUES 6
+#define NM_DIAG_V_MEAN_ACCEPT 0
+#define NM_DIAG_V_ENERGY_MEAN 1
+#define NM_DIAG_V_ENERGY_VAR 2
+#define NM_DIAG_V_BFMI 3
+#define NM_DIAG_V_MEAN_LOGP 4
+#define NM_DIAG_V_LAST_STEP_SIZE 5
+#define NM_DIAG_POOLED_COUNTS 8
+#define NM_DIAG_P_HEALTHY 0
+#define NM_DIAG_P_ROWS 1
+#define NM_DIAG_P_DIVERGING 2
+#define NM_DIAG_P_MAXDEPTH 3
+#define NM_DIAG_P_LEAPFROGS 4
+#define NM_DIAG_P_CHAINS_DIVERGING 5
+#define NM_DIAG_P_CHAINS_LOW_BFMI 6
+#define NM_DIAG_P_CHAINS_NAN_BFMI 7
+#define NM_DIAG_POOLED_VALUES 3
+#define NM_DIAG_PV_MEAN_ACCEPT 0
+#define NM_DIAG_PV_MEAN_STEP_SIZE 1
+#define NM_DIAG_PV_MIN_BFMI 2
+#define NM_DIAG_DEPTH_BINS 32
+typedef struct nm_diag_spec {
+    uint64_t n_draws;
+    uint64_t n_chains;
+    uint64_t phase;                /* NM_DIAG_ALL | NM_DIAG_SAMPLING (tuning == 0) | NM_DIAG_TUNING (tuning != 0) */
+    uint64_t max_events;           /* capacity of d_events, may be 0 */
+    double   bfmi_threshold;       /* a chain counts as "low" when bfmi < threshold (false for NaN) */
+    uint64_t reserved[3];
+} nm_diag_spec;
+typedef struct nm_diag_outputs {             /* device pointers, any may be NULL */
+    void*   d_chain_counts;    /* uint64_t[n_chains][NM_DIAG_CHAIN_COUNTS] */
+    double* d_chain_values;    /* [n_chains][NM_DIAG_CHAIN_VALUES] */
+    void*   d_pooled_counts;   /* uint64_t[NM_DIAG_POOLED_COUNTS] */
+    double* d_pooled_values;   /* [NM_DIAG_POOLED_VALUES] */
+    void*   d_depth_hist;      /* uint64_t[NM_DIAG_DEPTH_BINS] */
+    void*   d_events;          /* uint64_t[max_events][2] = (t, c) */
+    void*   d_n_events;        /* uint64_t[1]: ALL events, also those beyond max_events */
+    uint64_t reserved[3];
+} nm_diag_outputs;
+nm_status nm_stats_columns(uint64_t n_rows, uint64_t n_fields, const uint64_t* h_fields,
+                           const nm_draw_stats* d_stats, double* d_out, void* stream);
+nm_status nm_diagnose_stats(const nm_diag_spec* spec, const nm_draw_stats* d_stats, const nm_diag_outputs* out, void* stream);
+const char* nm_diag_last_error(void);
+
 const char* nm_last_error(void);
 uint64_t    nm_abi_version(void);
 

@@ -364,6 +364,25 @@ inline void pooled_scatter(const double* d_rows, uint64_t n_rows, uint64_t dim, 
     if (st != NM_OK) throw NutsError(st, nm_pooled_last_error());
 }
 
+// Statistics fields as a trace (nm_stats_columns; defined in nuts_amd.h): d_out[n_rows][fields.size()] = the words `fields` (positions of
+// the members in nm_draw_stats, < NM_STAT_WORDS) of every record as doubles, NaN for the records the engine did not write; with n_rows =
+// n_draws * n_chains the input of summarize_draws / quantile_draws / transform_draws.  `fields` may be freed on return.  Asynchronous on `stream`.
+inline void stats_columns(const nm_draw_stats* d_stats, uint64_t n_rows, const std::vector<uint64_t>& fields, double* d_out, void* stream = nullptr) {
+    const nm_status st = nm_stats_columns(n_rows, fields.size(), fields.data(), d_stats, d_out, stream);
+    if (st != NM_OK) throw NutsError(st, nm_diag_last_error());
+}
+
+// Per-chain and pooled sampler diagnostics and the divergence events of records that lie on the device (nm_diagnose_stats; defined in
+// nuts_amd.h).  phase NM_DIAG_ALL / NM_DIAG_SAMPLING / NM_DIAG_TUNING; max_events is the capacity of out.d_events.  Any output may be
+// null, not all.  Asynchronous on `stream`.
+inline void diagnose_stats(const nm_draw_stats* d_stats, uint64_t n_draws, uint64_t n_chains, const nm_diag_outputs& out,
+                           uint64_t phase = NM_DIAG_SAMPLING, uint64_t max_events = 0, double bfmi_threshold = 0.3, void* stream = nullptr) {
+    nm_diag_spec spec{};
+    spec.n_draws = n_draws; spec.n_chains = n_chains; spec.phase = phase; spec.max_events = max_events; spec.bfmi_threshold = bfmi_threshold;
+    const nm_status st = nm_diagnose_stats(&spec, d_stats, &out, stream);
+    if (st != NM_OK) throw NutsError(st, nm_diag_last_error());
+}
+
 struct ChainProgress {             // src/sampler.rs:1009-1051
     uint64_t finished_draws = 0, total_draws = 0, divergences = 0;
     bool tuning = true, started = false;

@@ -11,6 +11,8 @@ from .sampler import (AdamOptions, ChainBatch, DiagAdaptExpSettings, DiagNutsSet
                       LOGP_IID_NORMAL, LOGP_DIAG_NORMAL, LOGP_FUNNEL, LOGP_EIGHT_SCHOOLS, LOGP_MVN_PREC, LOGP_MODULE, LOGP_HOST_CALLBACK,
                       STEP_DUAL_AVERAGE, STEP_ADAM, STEP_FIXED)
 
+from ._lib import NM_DIAG_ALL, NM_DIAG_SAMPLING, NM_DIAG_TUNING, NM_DIAG_DEPTH_BINS, NM_STAT_WORDS  # noqa: F401
+from .sampler import SamplerDiagnostics, sampler_diagnostics, stats_columns  # noqa: F401
 from .pooled import covariance_draws, pooled_scatter  # noqa: F401
 from .controller import ChainProgress, ProgressCallback, Sampler, SamplerWaitResult  # noqa: F401
 
@@ -18,4 +20,5 @@ __all__ = ["ChainProgress", "ProgressCallback", "Sampler", "SamplerWaitResult", 
            "DiagAdaptExpSettings", "LowRankNutsSettings", "KineticEnergyKind", "DiagMclmcSettings", "LowRankMclmcSettings", "MclmcTrajectoryKind", "LowRankSettings", "LogpSpec", "Progress", "sample", "NutsAmdError", "STATS_DTYPE", "VECTOR_STATS",
            "load_library", "Summary", "summarize_draws", "NM_SUMMARY_CHUNK_CHAINS", "quantile_draws", "NM_QUANTILE_MAX_PROBS",
            "transform_draws", "rank_diagnostics", "RankDiagnostics", "RankSummary", "NM_RANK_SLAB_KEYS", "NM_TRANSFORM_RANK_NORMAL", "NM_TRANSFORM_FOLDED_RANK_NORMAL", "NM_TRANSFORM_INDICATOR_LE",
-           "covariance_draws", "pooled_scatter", "NM_SCATTER_SLAB_MIN_ROWS", "NM_SCATTER_MAX_SLABS", "NM_SCATTER_MAX_DIM"]
+           "covariance_draws", "pooled_scatter", "NM_SCATTER_SLAB_MIN_ROWS", "NM_SCATTER_MAX_SLABS", "NM_SCATTER_MAX_DIM",
+           "stats_columns", "sampler_diagnostics", "SamplerDiagnostics", "NM_STAT_WORDS", "NM_DIAG_ALL", "NM_DIAG_SAMPLING", "NM_DIAG_TUNING", "NM_DIAG_DEPTH_BINS"]

@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "nm_init_positions_uniform_at", "nm_engine_tile_launches", "nm_engine_lockstep_launches", "nm_engine_reduce_order", "nm_engine_host_logp_calls", "nm_pooled_partials", "nm_pooled_exchange", "nm_pooled_finish", "nm_pooled_last_error", "nm_pooled_scatter",
     "nm_logp_expanded_dim", "nm_engine_expanded_dim", "nm_engine_expand", "nm_summarize_draws", "nm_summary_last_error",
     "nm_quantile_draws", "nm_quantile_last_error", "nm_transform_draws", "nm_transform_last_error", "nm_rank_normal_score",
+    "nm_stats_columns", "nm_diagnose_stats", "nm_diag_last_error",
     # the per-vector `Math` seam
     "nm_math_create", "nm_math_destroy", "nm_math_dim", "nm_math_threads", "nm_math_last_error", "nm_vec_new", "nm_vec_free", "nm_vec_read_from_slice", "nm_vec_write_to_slice", "nm_vec_copy_into", "nm_vec_fill_array", "nm_vec_array_recip", "nm_vec_axpy_out", "nm_vec_axpy", "nm_vec_array_mult", "nm_vec_array_vector_dot", "nm_vec_scalar_prods3", "nm_vec_array_gaussian", "nm_vec_array_update_variance", "nm_vec_array_update_var_inv_std_draw_grad", "nm_vec_array_update_var_inv_std_grad", "nm_vec_array_update_var_inv_std_draw", "nm_vec_array_sum_ln", "nm_vec_array_all_finite", "nm_vec_logp_array", "nm_vec_sq_norm_sum", "nm_vec_std_norm_flow", "nm_vec_std_norm_grad_flow", "nm_vec_esh_momentum_update", "nm_vec_array_normalize",
 ]
@@ -140,6 +141,27 @@ class NmTransformSpec(C.Structure):
 
 class NmTransformOutputs(C.Structure):
     _fields_ = [("d_out", C.c_void_p), ("d_rank2", C.c_void_p), ("d_nan_count", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+# nm_stats_columns / nm_diagnose_stats: the words of a record, the phases, the columns of the outputs in ABI order (include/nuts_amd.h)
+NM_STAT_WORDS = 24
+NM_DIAG_ALL, NM_DIAG_SAMPLING, NM_DIAG_TUNING = 0, 1, 2
+NM_DIAG_CHAIN_COUNTS, NM_DIAG_CHAIN_VALUES, NM_DIAG_POOLED_COUNTS, NM_DIAG_POOLED_VALUES, NM_DIAG_DEPTH_BINS = 6, 6, 8, 3, 32
+(NM_DIAG_C_ROWS, NM_DIAG_C_DIVERGING, NM_DIAG_C_MAXDEPTH, NM_DIAG_C_LEAPFROGS, NM_DIAG_C_MAX_DEPTH, NM_DIAG_C_FINAL_STATUS) = range(6)
+(NM_DIAG_V_MEAN_ACCEPT, NM_DIAG_V_ENERGY_MEAN, NM_DIAG_V_ENERGY_VAR, NM_DIAG_V_BFMI, NM_DIAG_V_MEAN_LOGP, NM_DIAG_V_LAST_STEP_SIZE) = range(6)
+(NM_DIAG_P_HEALTHY, NM_DIAG_P_ROWS, NM_DIAG_P_DIVERGING, NM_DIAG_P_MAXDEPTH, NM_DIAG_P_LEAPFROGS, NM_DIAG_P_CHAINS_DIVERGING,
+ NM_DIAG_P_CHAINS_LOW_BFMI, NM_DIAG_P_CHAINS_NAN_BFMI) = range(8)
+NM_DIAG_PV_MEAN_ACCEPT, NM_DIAG_PV_MEAN_STEP_SIZE, NM_DIAG_PV_MIN_BFMI = 0, 1, 2
+DIAG_OUTPUTS = ("chain_counts", "chain_values", "pooled_counts", "pooled_values", "depth_hist", "events", "n_events")
+
+
+class NmDiagSpec(C.Structure):
+    _fields_ = [("n_draws", C.c_uint64), ("n_chains", C.c_uint64), ("phase", C.c_uint64), ("max_events", C.c_uint64),
+                ("bfmi_threshold", C.c_double), ("reserved", C.c_uint64 * 3)]
+
+
+class NmDiagOutputs(C.Structure):
+    _fields_ = [("d_" + k, C.c_void_p) for k in DIAG_OUTPUTS] + [("reserved", C.c_uint64 * 3)]
 
 
 # nm_lowrank_estimator_fn
@@ -316,6 +338,9 @@ def load():
     L.nm_transform_draws.argtypes = [C.POINTER(NmTransformSpec), vp, vp, C.POINTER(NmTransformOutputs), vp]
     L.nm_transform_last_error.restype = C.c_char_p
     L.nm_rank_normal_score.argtypes = [u64, u64, C.POINTER(dbl)]
+    L.nm_stats_columns.argtypes = [u64, u64, vp, vp, vp, vp]
+    L.nm_diagnose_stats.argtypes = [C.POINTER(NmDiagSpec), vp, C.POINTER(NmDiagOutputs), vp]
+    L.nm_diag_last_error.restype = C.c_char_p
     L.nm_last_error.restype = C.c_char_p
     L.nm_abi_version.restype = u64
     for name in ABI_SYMBOLS:

@@ -21,7 +21,7 @@ UNITS = ["kern_tile_mvn_prec.hip", "kern_tile_mvn_diag.hip", "kern_lockstep.hip"
          "kern_kin_diag_normal.hip@small", "kern_kin_funnel.hip@large", "kern_kin_funnel.hip@small", "kern_kin_host_cb.hip@large", "kern_kin_host_cb.hip@small", "kern_lane.hip",
          "kern_lane_kin.hip", "kern_iid_normal.hip@large", "kern_iid_normal.hip@small", "kern_diag_normal.hip@large", "kern_diag_normal.hip@small", "kern_funnel.hip@large",
          "kern_funnel.hip@small", "kern_host_cb.hip@large", "kern_host_cb.hip@small", "unit_batch.hip", "nuts_engine.hip", "kern_cluster.hip", "kern_cluster_kin.hip", "kern_eight_schools.hip@inl",
-         "kern_lr_eight_schools.hip@inl", "kern_kin_eight_schools.hip@inl", "math_seam.hip", "probe_bw.hip", "pooled_reduce.hip", "pooled_scatter.hip", "lowrank_device.hip", "kern_expand.hip@inl", "summary.hip", "quantile.hip", "rank_transform.hip@inl", "lowrank_host.cpp"]
+         "kern_lr_eight_schools.hip@inl", "kern_kin_eight_schools.hip@inl", "math_seam.hip", "probe_bw.hip", "pooled_reduce.hip", "pooled_scatter.hip", "lowrank_device.hip", "kern_expand.hip@inl", "summary.hip", "quantile.hip", "rank_transform.hip@inl", "stats_diag.hip", "lowrank_host.cpp"]
 # (lowrank_host.cpp holds both ISA builds of the host estimator in ONE translation unit: per-function target attributes, see there)
 # Variants of a unit ("file@variant": its own object, the flags below).  A density's one-chain kernels are TWO units from one source
 # (nuts_launch.hpp NM_TU_PART): "small" = the tilings of <= 4 doubles per lane + the small-chain kernels with EVERY special function inlined — no

@@ -528,7 +528,7 @@ class ChainBatch:
         self.synchronize()
         return out if is_tensor else out.cpu().numpy()
 
-    def draw_summary(self, n_draws, expanded=False, split=True, max_lag=32, quantiles=None, rank_normalized=False):
+    def draw_summary(self, n_draws, expanded=False, split=True, max_lag=32, quantiles=None, rank_normalized=False, diagnostics=False, stats=True):
         """n_draws draws of every chain into device buffers, summarised where they lie (summarize_draws): returns (Summary, stats
         [n_draws, n_chains] on the host).  Chains whose last chain_status is not NM_CHAIN_OK are left out of the summary.
         expanded=True summarises the expanded draws instead of the positions.  No position row crosses PCIe.
@@ -536,7 +536,11 @@ class ChainBatch:
         the same buffers and the same chains) and `quantile_probs`.  None (the default): neither is computed.
         rank_normalized=True: the result is a RankSummary, a Summary that also carries rhat_rank, ess_bulk, ess_tail and the two
         *_truncated flags (rank_diagnostics over the same buffers and the same chains).  False (the default): nothing more is launched,
-        the result is a plain Summary and the five read as None."""
+        the result is a plain Summary and the five read as None.
+        diagnostics=True: the summary's `sampler` is a SamplerDiagnostics of the same statistics buffer (sampler_diagnostics, phase
+        "all"); False (the default): nothing more is launched and it reads as None.
+        stats=False: None is returned in place of the host statistics and no statistics row crosses PCIe — the chains that are left
+        out come from the last row's chain_status alone (n_chains words)."""
         import torch
         dev = torch.device("cuda", self._device)                # the engine's device, whatever torch's current one is
         pos = torch.empty((n_draws, self.n_chains, self.logp.dim), dtype=torch.float64, device=dev)
@@ -550,9 +554,14 @@ class ChainBatch:
             if e.status != _lib.NM_ERR_LOGP_FAILURE:             # (stopped chains: the healthy ones' rows are there)
                 raise
         self.synchronize()
-        stats = st.cpu().numpy().view(STATS_DTYPE).reshape(n_draws, self.n_chains)
-        good = np.flatnonzero(stats["chain_status"][-1] == 0)
-        stats[stats["chain_status"] == np.uint64(2**64 - 1)] = np.zeros((), dtype=STATS_DTYPE)       # unwritten rows read as in draw_many
+        sampler = sampler_diagnostics(st, phase="all") if diagnostics else None
+        if stats:
+            stats = st.cpu().numpy().view(STATS_DTYPE).reshape(n_draws, self.n_chains)
+            good = np.flatnonzero(stats["chain_status"][-1] == 0)
+            stats[stats["chain_status"] == np.uint64(2**64 - 1)] = np.zeros((), dtype=STATS_DTYPE)       # unwritten rows read as in draw_many
+        else:                                                   # the last row's status alone, n_chains words: no statistics row crosses PCIe
+            final = sampler.final_status.astype(np.float64) if diagnostics else stats_columns(st[-1:], ["chain_status"]).cpu().numpy().reshape(-1)
+            good, stats = np.flatnonzero(final == 0), None
         ids = None if len(good) == self.n_chains else good
         summary = summarize_draws(ex if expanded else pos, split=split, max_lag=max_lag, chain_ids=ids)
         if quantiles is not None:
@@ -562,6 +571,8 @@ class ChainBatch:
             rd = rank_diagnostics(ex if expanded else pos, split=split, max_lag=max_lag, chain_ids=ids)
             summary = RankSummary(**{f.name: getattr(summary, f.name) for f in fields(summary)}, rhat_rank=rd.rhat_rank, ess_bulk=rd.ess_bulk,
                                   ess_tail=rd.ess_tail, ess_bulk_truncated=rd.ess_bulk_truncated, ess_tail_truncated=rd.ess_tail_truncated)
+        if diagnostics:
+            summary.sampler = sampler
         return summary, stats
 
     # ---- the low-rank transformation (LowRankNutsSettings; reference src/transform/low_rank.rs) ----
@@ -666,6 +677,8 @@ class Summary:
     quantile_probs: np.ndarray = None
     # the rank-normalised diagnostics are fields of RankSummary (below); a plain Summary keeps its field list and reads them as None
     rhat_rank = ess_bulk = ess_tail = ess_bulk_truncated = ess_tail_truncated = None
+    # a SamplerDiagnostics of the same buffers, only from draw_summary(..., diagnostics=True): attached, not a field
+    sampler = None
 
 
 @dataclass
@@ -830,6 +843,124 @@ def rank_diagnostics(draws, split=True, max_lag=32, chain_ids=None, max_scratch_
     return RankDiagnostics(rhat_rank=np.maximum(bulk.rhat, folded.rhat), ess_bulk=bulk.ess, ess_tail=np.minimum(lower.ess, upper.ess),
                            ess_bulk_truncated=bulk.ess_truncated, ess_tail_truncated=lower.ess_truncated | upper.ess_truncated,
                            nan_count=nan_count)
+
+
+DIAG_PHASES = {"all": _lib.NM_DIAG_ALL, "sampling": _lib.NM_DIAG_SAMPLING, "tuning": _lib.NM_DIAG_TUNING}
+DIAG_CHAIN_COUNTS = ("rows", "diverging", "maxdepth", "leapfrogs", "max_depth", "final_status")               # NM_DIAG_C_*
+DIAG_CHAIN_VALUES = ("mean_accept", "energy_mean", "energy_var", "bfmi", "mean_logp", "last_step_size")      # NM_DIAG_V_*
+DIAG_POOLED_COUNTS = ("healthy", "rows", "diverging", "maxdepth", "leapfrogs", "chains_diverging", "chains_low_bfmi", "chains_nan_bfmi")   # NM_DIAG_P_*
+DIAG_POOLED_VALUES = ("mean_accept", "mean_step_size", "min_bfmi")                                              # NM_DIAG_PV_*
+
+
+@dataclass
+class SamplerDiagnostics:
+    """Sampler diagnostics of recorded draw statistics (nm_diagnose_stats; defined by this repository, include/nuts_amd.h), on the
+    host.  Per chain [n_chains], over the written rows of the phase: the counts (uint64) and the values (float64; bfmi with ArviZ's
+    convention).  final_status is the chain_status of the last row whatever the phase: 0 = healthy, 2**64 - 1 = no row written.  The
+    pooled_* scalars run over the healthy chains; depth_hist[b] counts their rows with min(depth, 31) == b.  events: the (draw, chain)
+    pairs of the divergent rows of any chain in lexicographic order, the first min(n_events, max_events) of n_events."""
+    rows: np.ndarray
+    diverging: np.ndarray
+    maxdepth: np.ndarray
+    leapfrogs: np.ndarray
+    max_depth: np.ndarray
+    final_status: np.ndarray
+    mean_accept: np.ndarray
+    energy_mean: np.ndarray
+    energy_var: np.ndarray
+    bfmi: np.ndarray
+    mean_logp: np.ndarray
+    last_step_size: np.ndarray
+    pooled_healthy: int
+    pooled_rows: int
+    pooled_diverging: int
+    pooled_maxdepth: int
+    pooled_leapfrogs: int
+    pooled_chains_diverging: int
+    pooled_chains_low_bfmi: int
+    pooled_chains_nan_bfmi: int
+    pooled_mean_accept: float
+    pooled_mean_step_size: float
+    pooled_min_bfmi: float
+    depth_hist: np.ndarray
+    events: np.ndarray
+    n_events: int
+    phase: str = "sampling"
+
+
+def _stats_tensor(stats):
+    """the records as a uint8 CUDA tensor [n_draws, n_chains, sizeof(nm_draw_stats)]: a tensor is taken where it lies, a STATS_DTYPE
+    array [n_draws, n_chains] is uploaded once"""
+    import torch
+    if isinstance(stats, torch.Tensor):
+        if stats.dtype != torch.uint8 or stats.dim() != 3 or stats.shape[2] != STATS_DTYPE.itemsize or not stats.is_cuda:
+            raise ValueError(f"stats must be a uint8 CUDA tensor [n_draws, n_chains, {STATS_DTYPE.itemsize}] or a STATS_DTYPE array")
+        return stats.contiguous()
+    a = np.ascontiguousarray(stats, dtype=STATS_DTYPE)
+    if a.ndim != 2:
+        raise ValueError("stats must be a STATS_DTYPE array [n_draws, n_chains]")
+    return torch.from_numpy(a.view(np.uint8).reshape(a.shape + (STATS_DTYPE.itemsize,))).cuda()
+
+
+def stats_columns(stats, fields):
+    """Statistics fields as a trace (nm_stats_columns, include/nuts_amd.h), on the GPU: `fields` are names of STATS_DTYPE, the result
+    is a float64 CUDA tensor [n_draws, n_chains, len(fields)] — the input of summarize_draws, quantile_draws and transform_draws
+    (e.g. the R-hat and ESS of lp__ and energy from ["logp", "energy"]).  Integer fields are converted, every field of a row the
+    engine did not write (chain_status all ones) is NaN.  stats: a uint8 CUDA tensor [n_draws, n_chains, 192] read where it lies, or
+    a STATS_DTYPE array [n_draws, n_chains] uploaded once."""
+    import torch
+    t = _stats_tensor(stats)
+    N, Cn = int(t.shape[0]), int(t.shape[1])
+    names = list(STATS_DTYPE.names)
+    for f in fields:
+        if f not in names:
+            raise ValueError(f"unknown statistic {f!r}")
+    idx = np.array([names.index(f) for f in fields], dtype=np.uint64)
+    with torch.cuda.device(t.device):
+        out = torch.empty((N, Cn, len(idx)), dtype=torch.float64, device=t.device)
+        torch.cuda.current_stream(t.device).synchronize()       # the call runs on the null stream: the rows must be there
+        L = _lib.load()
+        _lib.check_status(L.nm_stats_columns(N * Cn, len(idx), idx.ctypes.data if len(idx) else None, C.c_void_p(t.data_ptr() or None),
+                                             C.c_void_p(out.data_ptr() or None), None), L.nm_diag_last_error)
+        torch.cuda.synchronize(t.device)
+    return out
+
+
+def sampler_diagnostics(stats, phase="sampling", max_events=4096, bfmi_threshold=0.3) -> SamplerDiagnostics:
+    """Per-chain and pooled sampler diagnostics and the divergence events of recorded statistics (nm_diagnose_stats), computed on the
+    GPU where the records lie: only the results cross PCIe.  phase: "all", "sampling" (tuning == 0) or "tuning".  stats as in
+    stats_columns; rows of chains that may have stopped must read as unwritten (a buffer filled with 0xFF before the draw call, as
+    draw_summary's is)."""
+    import torch
+    if phase not in DIAG_PHASES:
+        raise ValueError(f"phase must be one of {sorted(DIAG_PHASES)}")
+    t = _stats_tensor(stats)
+    N, Cn = int(t.shape[0]), int(t.shape[1])
+    max_events = int(max_events)
+    spec = _lib.NmDiagSpec(N, Cn, DIAG_PHASES[phase], max_events, float(bfmi_threshold))
+    with torch.cuda.device(t.device):
+        i64 = lambda *shape: torch.empty(shape, dtype=torch.int64, device=t.device)          # noqa: E731
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=t.device)        # noqa: E731
+        bufs = dict(chain_counts=i64(Cn, _lib.NM_DIAG_CHAIN_COUNTS), chain_values=f64(Cn, _lib.NM_DIAG_CHAIN_VALUES),
+                    pooled_counts=i64(_lib.NM_DIAG_POOLED_COUNTS), pooled_values=f64(_lib.NM_DIAG_POOLED_VALUES),
+                    depth_hist=i64(_lib.NM_DIAG_DEPTH_BINS), events=i64(max_events, 2) if max_events > 0 else None, n_events=i64(1))
+        out = _lib.NmDiagOutputs()
+        for k, b in bufs.items():
+            setattr(out, "d_" + k, (b.data_ptr() or None) if b is not None else None)
+        torch.cuda.current_stream(t.device).synchronize()       # the call runs on the null stream: the rows must be there
+        L = _lib.load()
+        _lib.check_status(L.nm_diagnose_stats(C.byref(spec), C.c_void_p(t.data_ptr() or None), C.byref(out), None), L.nm_diag_last_error)
+        torch.cuda.synchronize(t.device)
+    u64 = lambda b: b.cpu().numpy().view(np.uint64)              # noqa: E731
+    cc, cv, pc, pv = u64(bufs["chain_counts"]), bufs["chain_values"].cpu().numpy(), u64(bufs["pooled_counts"]), bufs["pooled_values"].cpu().numpy()
+    n_events = int(u64(bufs["n_events"])[0])
+    n_kept = min(n_events, max_events)
+    events = u64(bufs["events"][:n_kept]) if max_events > 0 else np.zeros((0, 2), dtype=np.uint64)
+    named = {k: np.ascontiguousarray(cc[:, i]) for i, k in enumerate(DIAG_CHAIN_COUNTS)}
+    named.update({k: np.ascontiguousarray(cv[:, i]) for i, k in enumerate(DIAG_CHAIN_VALUES)})
+    named.update({"pooled_" + k: int(pc[i]) for i, k in enumerate(DIAG_POOLED_COUNTS)})
+    named.update({"pooled_" + k: float(pv[i]) for i, k in enumerate(DIAG_POOLED_VALUES)})
+    return SamplerDiagnostics(depth_hist=u64(bufs["depth_hist"]), events=events, n_events=n_events, phase=phase, **named)
 
 
 def sample(settings: DiagNutsSettings, logp: LogpSpec, x0=None, chain_id_offset=0, device=-1, chunk_bytes=0, expanded=False):

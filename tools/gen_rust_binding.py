@@ -20,7 +20,8 @@ STRUCT_NAMES = {"nm_settings": "NmSettings", "nm_logp_spec": "NmLogpSpec", "nm_e
                 "nm_draw_stats": "NmDrawStats", "nm_draw_outputs": "NmDrawOutputs",
                 "nm_summary_spec": "NmSummarySpec", "nm_summary_outputs": "NmSummaryOutputs",
                 "nm_quantile_spec": "NmQuantileSpec", "nm_quantile_outputs": "NmQuantileOutputs",
-                "nm_transform_spec": "NmTransformSpec", "nm_transform_outputs": "NmTransformOutputs"}
+                "nm_transform_spec": "NmTransformSpec", "nm_transform_outputs": "NmTransformOutputs",
+                "nm_diag_spec": "NmDiagSpec", "nm_diag_outputs": "NmDiagOutputs"}
 OPAQUE = {"nm_engine": "NmEngine", "nm_math": "NmMath", "nm_vec": "NmVec"}
 SCALARS = {"uint64_t": "u64", "int64_t": "i64", "double": "f64", "uint8_t": "u8", "char": "c_char", "void": "c_void", "int": "i32"}
 FN_PTRS = {"nm_host_logp_fn": "Option<NmHostLogpFn>", "nm_lowrank_estimator_fn": "Option<NmLowrankEstimatorFn>"}
