@@ -60,6 +60,9 @@ template <int DPL, int W, class Dens> constexpr bool nog_mode();
 // the top-level test has six loads per iteration and looks at most NM_TEST_CHUNK3_MAX ahead
 constexpr int NM_TEST_CHUNK = 4;
 constexpr int NM_TEST_CHUNK3_MAX = 2;
+// (gradient-free points) pairs of the initial point's g_z a leapfrog that starts there requests ahead of the pair it computes: measured 1 / 4 / 8
+// (profiles/r19_k2_start_point_loads_ab.txt); 8 = the whole tile of the 16-doubles tiling, requested before the first pair
+constexpr int NM_G2_AHEAD = 8;
 
 // Phase timing for development (-DNM_PROF=1): block 0 accumulates shader-clock cycles between marks into P.prof[].
 #ifndef NM_PROF
@@ -1013,7 +1016,8 @@ NM_DEV void leapfrog_kin(ChainCtx<DPL, W, Dens>& C, const Pt<DPL>& s, Pt<DPL>& o
 // multiply-adds as inline asm: it is where the instruction pays (K2 +5 %: profiles/r05u), and every failing build of DESIGN §22's fourth
 // incident had the asm form at the MCLMC site.
 // GMODE (round 6, nog_mode): where the start point's g_z comes from — 0: its tile s.g; 1: recomputed from s.z (element-wise densities: the operations that
-// produced it); 2: streamed from the slot `gsrc` (the trajectory's initial point: P_GZ).  With GMODE != 0 neither s.g nor o.g is touched.
+// produced it); 2: read from the slot `gsrc` (the trajectory's initial point: P_GZ), NM_G2_AHEAD pairs ahead of the pair that uses them; 3: the
+// shared tile *gshared.  With GMODE != 0 neither s.g nor o.g is touched: the end point's g_z goes to *gshared.
 template <int DPL, int W, class Dens, int SITE = 0, int GMODE = 0>
 NM_DEV void leapfrog(ChainCtx<DPL, W, Dens>& C, const Pt<DPL>& s, Pt<DPL>& o, double epsilon, Tile<DPL>* x_out, Tile<DPL>* gx_out,
                      typename ChainCtx<DPL, W, Dens>::SlotRef gsrc = typename ChainCtx<DPL, W, Dens>::SlotRef{}, Tile<DPL>* gshared = nullptr) {
@@ -1064,14 +1068,22 @@ NM_DEV void leapfrog(ChainCtx<DPL, W, Dens>& C, const Pt<DPL>& s, Pt<DPL>& o, do
         auto pass = [&](auto full_tile) __attribute__((always_inline)) {
             constexpr bool FULL = decltype(full_tile)::value;
             double2 sg = sg2[0], mm = mu2[0];
-            [[maybe_unused]] double2 gg = make_double2(0., 0.);
-            if constexpr (GMODE == 2) gg = C.ld2(gsrc.r, gsrc.so, 0);
+            // GMODE 2 (round 11): the slot's rows land GA pairs ahead of the pair that consumes them — rows 0 .. GA-1 are requested before the first
+            // pair, then pair m takes its row and requests row m + GA into the registers it has just freed.  One row ahead (rounds 6-10) left a lone
+            // wavefront a memory round trip per two pairs: a pair is ~120 cycles, the row ~200-900 away.
+            constexpr int GA = GMODE == 2 ? (NM_G2_AHEAD < DPL / 2 ? NM_G2_AHEAD : DPL / 2) : 1;
+            [[maybe_unused]] double2 ggb[GA];
+            if constexpr (GMODE == 2) {
+#pragma unroll
+                for (int c = 0; c < GA; ++c) ggb[c] = C.ld2(gsrc.r, gsrc.so, c);
+                __builtin_amdgcn_sched_barrier(0);
+            }
 #pragma unroll
             for (int m = 0; m < DPL / 2; ++m) {
                 const double2 sg_c = sg, mm_c = mm;
-                [[maybe_unused]] const double2 gg_c = gg;
+                [[maybe_unused]] double2 gg_c = make_double2(0., 0.);
+                if constexpr (GMODE == 2) gg_c = ggb[m % GA];
                 if (m + 1 < DPL / 2) { sg = sg2[(m + 1) * 64 * W]; mm = mu2[(m + 1) * 64 * W]; }      // the next pair's sigma / mu are in flight during this pair
-                if constexpr (GMODE == 2) { if (m + 1 < DPL / 2) gg = C.ld2(gsrc.r, gsrc.so, m + 1); }
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int k = 2 * m + j;
@@ -1112,6 +1124,7 @@ NM_DEV void leapfrog(ChainCtx<DPL, W, Dens>& C, const Pt<DPL>& s, Pt<DPL>& o, do
                     if (x_out) x_out->a[k] = xk;
                     if (gx_out) gx_out->a[k] = gxk;
                 }
+                if constexpr (GMODE == 2) { if (m + GA < DPL / 2) ggb[m % GA] = C.ld2(gsrc.r, gsrc.so, m + GA); }
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
