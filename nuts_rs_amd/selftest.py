@@ -10,7 +10,7 @@ Called by nuts_rs_amd.build.build() when a GPU is present, by __graft_entry__.sm
 NM_LOGP_MODULE engine is created (sampler.ChainBatch): a library or runtime that no longer reproduces the answers fails loudly.
 
 Round 6: EVERY instantiation of the one-chain-per-block kernels has its own known answer
-(selftest_instantiations.json: 328 runs — density x settings family x tiling x both ends of the tiling's dims —, the oracle's SHA-256 of
+(selftest_instantiations.json: 349 runs — density x settings family x tiling x both ends of the tiling's dims —, the oracle's SHA-256 of
 every position and exact statistic; cases in selftest_cases.py).  `run_all()` checks all of them (build() on a GPU box; ~1 min);
 `first_use(batch)` checks the runs of the ONE instantiation an engine is about to launch, the first time a process creates such an engine
 (~0.1 - 0.3 s; sampler.ChainBatch calls it; NUTS_AMD_SELFTEST=0 turns it off).  The wrong-results incidents of rounds 4 - 5
@@ -153,16 +153,22 @@ def run_all(verbose=False, device=-1, only=None):
     from . import selftest_cases as SC
     bad = []
     n = 0
+    open_cases = {}            # instantiation -> its cases that have not passed in this call (skipped by `only`, or failed)
     for c in SC.cases():
+        key = (c["dens"], c["fam"], c["dpl"], c["w"])
+        open_cases[key] = open_cases.get(key, 0) + 1
         if only and only not in SC.case_id(c):
             continue
         msg = check_case(c, device)
         n += 1
         if msg:
             bad.append(msg)
-        elif verbose:
+            continue
+        if verbose:
             print("self-test", SC.case_id(c), "ok")
-        _checked.add((c["dens"], c["fam"], c["dpl"], c["w"]))
+        open_cases[key] -= 1
+    # an instantiation counts as verified only when EVERY one of its cases passed: a failed one is checked again by first_use
+    _checked.update(key for key, left in open_cases.items() if left == 0)
     if bad:
         raise SelfTestError(f"{len(bad)} of {n} kernel instantiations of the built library do not reproduce their known answers:\n  " + "\n  ".join(bad[:40]) +
                             "\nthis build (compiler, flags, headers) is not the one the parity suite verified; see DESIGN §22")
@@ -183,7 +189,6 @@ def first_use(batch, device=-1):
         key = (dens, fam, dpl, w)
         if key in _checked:
             continue
-        _checked.add(key)
         for c in SC.cases():
             if (c["dens"], c["fam"], c["dpl"], c["w"]) == key:
                 msg = check_case(c, device)
@@ -191,6 +196,7 @@ def first_use(batch, device=-1):
                 if msg:
                     raise SelfTestError("the kernel instantiation this engine is about to launch does not reproduce its known answer: " + msg +
                                         "; the library was built by a compiler / from headers other than the verified ones (DESIGN §22), or the runtime differs")
+        _checked.add(key)          # only now: after a failure the next engine of this instantiation is checked, and refused, again
     return n
 
 

@@ -249,6 +249,18 @@ class Chain:
     def set_position(self, x0):
         return lib().nmo_chain_set_position(self._h, np.ascontiguousarray(x0, dtype=np.float64))
 
+    def set_transform(self, stds, mean, vals, vecs, mu_lr):
+        """`LowRankMassMatrix::update` on this chain's transformation (vecs: [n_eig][dim]), where `run(transform=...)` applies it: right
+        after a successful set_position.  Returns 1 if it was applied, 0 if update() bailed out on non-finite input."""
+        (stds, mean, vals, vecs, mu_lr), n_eig, per_chain = _transform_arrays((stds, mean, vals, vecs, mu_lr), 1, self.dim)
+        assert not per_chain
+        return lib().nmo_chain_set_transform(self._h, stds, mean, n_eig, vals if n_eig else np.zeros(1), vecs if n_eig else np.zeros(1), mu_lr)
+
+    def set_estimator(self, fn, ctx=None):
+        """LowRankMassMatrixStrategy's dense linear algebra: an ESTIMATOR_FN (before set_position, as `run(estimator=...)` sets it)."""
+        self._est = fn
+        lib().nmo_chain_set_estimator(self._h, fn, ctx)
+
     def draw(self):
         pos = np.empty(self.dim)
         st = np.zeros(1, dtype=STATS_DTYPE)

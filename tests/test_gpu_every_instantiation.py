@@ -15,7 +15,10 @@ Two tests: `test_instantiation_bit_exact` on the dyadic inputs of the library's 
 `test_instantiation_bit_exact_generic_inputs` on full-mantissa doubles (the top end of every tiling), where no product is exact by construction.
 
 What is covered per instantiation, and where: the one-chain-per-block family here; the several-chains-per-wavefront family (both register
-allocations of every kernel) and the one-chain-per-lane family in test_gpu_small_chain_instantiations.py.  The matrix-core tile kernels, the
+allocations of every kernel) and the one-chain-per-lane family in test_gpu_small_chain_instantiations.py; the host-callback family (HostCb,
+LrWrap<HostCb>, KinWrap<HostCb> on the same eight tilings) in test_gpu_host_callback_instantiations.py.  That family has no known answers as
+data, because a Python callback has none (selftest_cases.DENSITIES leaves it out, `selftest.first_use` runs nothing for such an engine): oracle
+parity in that file is its only guard.  The matrix-core tile kernels, the
 lockstep kernel and the cluster kernels (chains wider than one block) have few instantiations and rest on the hand-picked cases of their own files
 (test_gpu_tile_diag.py, test_gpu_lowrank.py, test_gpu_wide_chains.py)."""
 import ctypes as C

@@ -25,17 +25,24 @@ def banana(chain, x):
     return lp, g
 
 
-def run_both(oracle, fn_engine, fn_oracle, dim, n, tune, draws, seed=3, low_rank=False, **skw):
+def run_both(oracle, fn_engine, fn_oracle, dim, n, tune, draws, seed=3, low_rank=False, dims_per_lane=0, waves_per_chain=0, **skw):
+    """`dims_per_lane` / `waves_per_chain`: the engine's tiling (0: its own choice); the oracle sums in the order of the tiling the engine reports."""
     s = (N.LowRankNutsSettings if low_rank else N.DiagNutsSettings)(num_chains=n, seed=seed, num_tune=tune, store_divergences=True, **skw)
     logp = N.LogpSpec.host_callback(dim, fn_engine, threads=2)
-    b = N.ChainBatch(s, logp, n)
+    b = N.ChainBatch(s, logp, n, dims_per_lane=dims_per_lane, waves_per_chain=waves_per_chain)
+    if dims_per_lane or waves_per_chain:
+        assert (b.dims_per_lane(), b.threads_per_chain() // 64) == (dims_per_lane, waves_per_chain) and b.blocks_per_chain() == 1
     x0 = b.init_positions_uniform()
     status = b.set_position(x0, raise_on_error=False)
     pos, st = b.draw_many(draws, raise_on_error=False)
     calls = b.host_logp_calls()
     tpc = b.threads_per_chain()
     b.close()
+    return status, pos, st, run_oracle_chains(oracle, fn_oracle, s, dim, n, draws, x0, tpc), calls
 
+
+def run_oracle_chains(oracle, fn_oracle, s, dim, n, draws, x0, tpc):
+    """The oracle's side of `run_both`: per chain (status of set_position, [(position, statistics, status) of every draw up to the one that stops it])."""
     def tramp(ctx, d, px, pg, plogp):
         try:
             lp, g = fn_oracle(0, np.ctypeslib.as_array(px, shape=(d,)).copy())
@@ -60,7 +67,7 @@ def run_both(oracle, fn_engine, fn_oracle, dim, n, tune, draws, seed=3, low_rank
                 if rc2 != 0:
                     break
         res.append((rc, rows))
-    return status, pos, st, res, calls
+    return res
 
 
 def compare(status, pos, st, res, allow_stop=False):

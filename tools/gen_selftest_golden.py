@@ -7,7 +7,7 @@ tests/test_oracle_golden.py), generated once and committed; regenerate only when
 * nuts_rs_amd/selftest_golden.json: last positions' bits + every draw's n_steps / depth of two small runs that the
   wave, group and lane kernels all serve.
 * nuts_rs_amd/selftest_instantiations.json: for EVERY (density, settings family, tiling) of the one-chain-per-block
-  kernels, at both ends of the tiling's range of dims (nuts_rs_amd/selftest_cases.py: 328 runs), the SHA-256 of every position and exact
+  kernels, at both ends of the tiling's range of dims (nuts_rs_amd/selftest_cases.py: 349 runs), the SHA-256 of every position and exact
   statistic of a short adaptive run, plus the leapfrog count.  Needs no GPU: the summation order of a wave kernel is fixed by its tiling
   (threads per chain = 64 x wavefronts), and the low-rank estimator the adapting cases use is the library's host twin."""
 import ctypes as C

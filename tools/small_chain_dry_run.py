@@ -1,9 +1,12 @@
-"""Oracle-only dry run (no GPU) of the case lists of tests/test_gpu_small_chain_instantiations.py and of
-`test_instantiation_bit_exact_generic_inputs` (tests/test_gpu_every_instantiation.py): those tests skip nothing, so every case must be one in
-which the oracle accepts every initial point and no sampled chain fails.  A case reported here gets another seed in the test file's
-SEEDS / GENERIC_SEEDS.
+"""Oracle-only dry run (no GPU) of the case lists of tests/test_gpu_small_chain_instantiations.py, of
+`test_instantiation_bit_exact_generic_inputs` (tests/test_gpu_every_instantiation.py) and of tests/test_gpu_host_callback_instantiations.py:
+those tests skip nothing, so every case must be one in which the oracle accepts every initial point and no sampled chain fails.  A case
+reported here gets another seed in the test file's SEEDS / GENERIC_SEEDS / TAX_SEEDS.
 
-    python tools/small_chain_dry_run.py [--cus 256] [--only small|generic]"""
+The host-callback pass also reports a case whose trees stay below depth 3, an error-taxonomy case whose wall or fatal region is never met
+(or in which no chain is left to go on), and prints the oracle's wall time of every case.
+
+    python tools/small_chain_dry_run.py [--cus 256] [--only small|generic|hostcb]"""
 import argparse
 import ctypes as C
 import os
@@ -60,21 +63,63 @@ def generic():
     return len(cases), chains, bad
 
 
+def hostcb():
+    import test_gpu_host_callback_instantiations as H
+    from helpers import estimator_pair
+    from nuts_rs_amd import selftest_cases as SC
+    bad, cases = [], H.hostcb_cases()
+    for c in cases:
+        cid = SC.case_id(c)
+        if H.tiling_id(c) in H.REFUSED:
+            print(f"  {cid}: refused by the engine's plan ({H.REFUSED[H.tiling_id(c)]})")
+            continue
+        s, draws, adapting = H.make_run(c)
+        x0 = O.init_positions_uniform(s.seed, 0, H.N_CHAINS, c["dim"])
+        est = estimator_pair(O)[0] if adapting else None
+        pos, st, failed, secs = H.oracle_side(O, c, s, draws, x0, 64 * c["w"], 0, est)
+        why = []
+        if failed or not (st["chain_status"] == 0).all() or not np.isfinite(pos).all():
+            why.append(f"chains {failed} rejected their initial point or failed")
+        elif st["depth"].max() < 3:
+            why.append(f"depth.max() = {int(st['depth'].max())} < 3")
+        print(f"  {cid}: {secs:.2f} s, {int(st['n_steps'].sum())} leapfrogs, depth <= {int(st['depth'].max())}, {int(st['diverging'].sum())} divergent draws"
+              + "".join("  <-- " + w for w in why))
+        if why:
+            bad.append(cid)
+    tax = H.taxonomy_cases()
+    for c in tax:
+        t = time.time()
+        res = H.taxonomy_oracle(O, c)
+        why = H.taxonomy_findings(c, res)
+        stopped = {k: len(rows) - 1 for k, (rc, rows) in enumerate(res) if rows and rows[-1][2] != 0}
+        nan_div = sum(1 for rc, rows in res for (_, q, rc2) in rows if rc2 == 0 and q["diverging"] and np.isnan(q["divergence_energy_error"]))
+        print(f"  {H.taxonomy_id(c)}: {time.time() - t:.2f} s, {nan_div} divergent draws without an energy error, chains stopped (chain: draw) {stopped}"
+              + "".join("  <-- " + w for w in why))
+        if why:
+            bad.append(H.taxonomy_id(c))
+    return len(cases), len(tax), bad
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--cus", type=int, default=256)
-    ap.add_argument("--only", choices=["small", "generic"])
+    ap.add_argument("--only", choices=["small", "generic", "hostcb"])
     a = ap.parse_args()
     O.lib()
     rc = 0
-    if a.only != "generic":
+    if a.only in (None, "small"):
         t = time.time()
         n, chains, div, bad = small(a.cus)
         print(f"small-chain matrix: {n} cases, {chains} oracle chains, {div} divergent draws, {len(bad)} cases with a failed chain {bad}, {time.time() - t:.1f} s")
         rc |= bool(bad)
-    if a.only != "small":
+    if a.only in (None, "generic"):
         t = time.time()
         n, chains, bad = generic()
         print(f"generic inputs: {n} cases, {chains} oracle chains, {len(bad)} cases with a failed chain {bad}, {time.time() - t:.1f} s")
+        rc |= bool(bad)
+    if a.only in (None, "hostcb"):
+        t = time.time()
+        n, n_tax, bad = hostcb()
+        print(f"host-callback instantiations: {n} cases + {n_tax} error-taxonomy cases, {len(bad)} cases reported {bad}, {time.time() - t:.1f} s")
         rc |= bool(bad)
     sys.exit(rc)
