@@ -2107,6 +2107,18 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
         int stop = STOP_NONE;
         double sub_log_size = 0.;
         CandRef sub_cand = {-2, 0., 0., 0};
+        // Round 12 (RE && NOG): the end point the last doubling produced is written to its registers HERE, at the head of the doubling that follows it,
+        // not where the merge accepted it.  O still holds it (o_is_edge; nothing between the merge and this line writes O, and every reader of
+        // MLz .. MRv — the reload below, the top-level tests — comes after this line), and a draw that ends before another doubling never reads it.
+        // Written at the merge, the tiles changed on one of several paths into the loop's latch and the allocator gave them a second home there:
+        // every doubling copied all four tiles out and back (profiles/r20_k2_doubling_boundary_ab.txt).  Two `if`s, not if / else: with an
+        // else arm the compiler routes the unchanged side through the join as well (same file, form e3).
+        if constexpr (RE && NOG) {
+            if (o_is_edge) {
+                if (o_edge_sign > 0) { asm volatile("; new right end"); MRz.put(O.z); MRv.put(O.v); }
+                if (o_edge_sign < 0) { asm volatile("; new left end"); MLz.put(O.z); MLv.put(O.v); }
+            }
+        }
         const bool reuse_edge = o_is_edge && o_edge_sign == sign;
         o_is_edge = false;               // O is about to be overwritten; set again only by a successful merge
 
@@ -2668,7 +2680,8 @@ NM_DEV uint64_t nuts_transition(ChainCtx<DPL, W, Dens>& C, AcceptCollector& col,
             if (ns == 0) ns = other_side == 1 ? 2 : 1;          // id 0 (the initial point) is read-only
             if constexpr (RE) {
                 if constexpr (!NOG) C.storeRef(O.g, C.edge_g(ns));
-                if (fwd) { asm volatile("; new right end"); MRz.put(O.z); MRv.put(O.v); } else { asm volatile("; new left end"); MLz.put(O.z); MLv.put(O.v); }
+                // (NOG: the registers are written at the head of the next doubling, see there)
+                if constexpr (!NOG) { if (fwd) { asm volatile("; new right end"); MRz.put(O.z); MRv.put(O.v); } else { asm volatile("; new left end"); MLz.put(O.z); MLv.put(O.v); } }
             } else {
             C.storeRef(O.z, C.edge_z(ns)); C.storeRef(O.v, C.edge_v(ns)); if constexpr (!NOG) C.storeRef(O.g, C.edge_g(ns));
             }
