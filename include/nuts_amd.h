@@ -304,7 +304,11 @@ typedef struct nm_draw_stats {
  * their position rows hold (NaN through the *_to_host calls).  The expansion never touches a chain's random stream.
  * Event rows are written only on the draws where the event happens (stats.transformation_update_id >= 0, resp.
  * stats.diverging != 0); other rows are left untouched.  `divergence_momentum` is always None on this path
- * (start_momentum: None, src/dynamics/transformed_hamiltonian.rs:567, :596) and has no buffer. */
+ * (start_momentum: None, src/dynamics/transformed_hamiltonian.rs:567, :596) and has no buffer.
+ * One kernel does not write the event rows: the lockstep matrix-core kernel (nm_engine_config.chain_tiles) records positions, statistics,
+ * d_gradient and the transformed point only, and a draw call that hands it one of the divergence or mass-matrix buffers returns
+ * NM_ERR_UNSUPPORTED before anything is launched.  An engine whose settings set store_divergences or store_mass_matrix never chooses that
+ * kernel by itself; chain_tiles = 2 excludes it. */
 typedef struct nm_draw_outputs {
     double*        d_positions;               /* the draws (State::write_position, src/chain.rs:163-164) */
     nm_draw_stats* d_stats;                   /* [n_draws][n_chains] */
@@ -340,7 +344,10 @@ typedef struct nm_engine_config {
                                     * products on the matrix cores (v_mfma_f64_16x16x4_f64), same results.  (a) DiagNutsSettings: P x of the density,
                                     * every chain keeps its own adapting mass matrix; (b) one low-rank transformation shared by all chains
                                     * (nm_engine_set_transform per_chain = 0, freeze_transform; dim and rank multiples of 8): U'z, U s and P x.
-                                    * 0 = auto ((a) from 256 chains on, (b) whenever it applies), 1 = never, 2 = whenever it applies */
+                                    * 0 = auto ((a) from 256 chains on, (b) whenever it applies), 1 = never, 2 = whenever it applies.
+                                    * (b) has two kernels: one wavefront per chain (every vector of nm_draw_outputs), and a lockstep form that the
+                                    * automatic choice takes when the settings store neither divergences nor the mass matrix (it does not write
+                                    * those vectors: see nm_draw_outputs); 2 = always the former, 3 = the lockstep form or NM_ERR_UNSUPPORTED */
     uint64_t lowrank_max_rank;     /* NM_ADAPT_LOW_RANK: eigenvector slots per chain (HBM: (max_rank + 1) x dim f64 per chain).
                                     * 0 = auto: min(dim, 2 (num_tune + 1)) — the most the reference's estimator can return — or dim with freeze_transform */
     uint64_t lane_chains;          /* chains with dim <= 10: ONE CHAIN PER LANE, 64 chains per wavefront (nuts_lane.hpp), same results.  DiagNutsSettings,

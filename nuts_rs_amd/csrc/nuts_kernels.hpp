@@ -2757,10 +2757,19 @@ NM_DEV void emit_divergence_vectors(ChainCtx<DPL, W, Dens>& C, int64_t start_idx
     }
     write_row(C, P.out_div_start, row, x);
     write_row(C, P.out_div_start_grad, row, gx);
-    if (!has_end) return;
+    // The tile kernel's products are rendezvous of the block's 16 chains in whole (apply, density, apply) cadences (nuts_tile.hpp).  A start
+    // point that is rebuilt takes an apply and a density round and the end point the closing apply; a start point read from P_X leaves the end
+    // point's apply alone in its cadence, and the wavefront then met the other chains' density round with an apply: their leapfrogs read
+    // garbage.  The missing rounds are attended with an empty column.
+    if (!has_end) {
+        if constexpr (tile_trait<Dens>::value) { if (start_idx != 0) C.dens.tile_skip_apply(); }
+        return;
+    }
     C.loadS(zt, slot_F(0) + 1);
-    if constexpr (lr_trait<Dens>::value) transform_to_x(C, zt, x);
-    else {
+    if constexpr (lr_trait<Dens>::value) {
+        transform_to_x(C, zt, x);
+        if constexpr (tile_trait<Dens>::value) { if (start_idx == 0) { C.dens.tile_skip_density(); C.dens.tile_skip_apply(); } }
+    } else {
 #pragma unroll
     for (int k = 0; k < DPL; ++k) x.a[k] = __builtin_fma(1.0, mu.a[k], zt.a[k] * sig.a[k]);
     }

@@ -263,6 +263,7 @@ struct TileMvnPrec {
     template <int DPL>
     NM_DEV void tile_apply(int which, Tile<DPL>& v) { (void)apply_round(*X, which, &v, false); }
     NM_DEV void tile_skip_density() { density_round<4>(*X, (const Tile<4>*)nullptr, (Tile<4>*)nullptr); }
+    NM_DEV void tile_skip_apply() { (void)apply_round<4>(*X, 0, (Tile<4>*)nullptr, false); }
     template <int DPL, int W>
     NM_DEV double eval(const Tile<DPL>& x, Tile<DPL>& gx, int dim, Reducer<W>& R) const {
         Tile<DPL> xs, y;

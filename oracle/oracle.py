@@ -134,6 +134,8 @@ def lib():
     L.nmo_chain_set_position.restype = C.c_int
     L.nmo_chain_draw.argtypes = [C.c_void_p, _dp, C.c_void_p]
     L.nmo_chain_draw.restype = C.c_int
+    L.nmo_chain_draw_ex.argtypes = [C.c_void_p, _dp, C.c_void_p, C.POINTER(DrawVectors)]
+    L.nmo_chain_draw_ex.restype = C.c_int
     L.nmo_chain_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.nmo_run.restype = C.c_int
@@ -261,10 +263,19 @@ class Chain:
         self._est = fn
         lib().nmo_chain_set_estimator(self._h, fn, ctx)
 
-    def draw(self):
+    def draw(self, vectors=None):
+        """vectors: optional dict that receives this draw's vector-valued statistics, one [dim] row per name of VECTOR_STATS (NaN-filled;
+        an event row is written only when the event happens in this draw): `Chain::expanded_draw`, as `run(vectors=...)` fills its rows."""
         pos = np.empty(self.dim)
         st = np.zeros(1, dtype=STATS_DTYPE)
-        rc = lib().nmo_chain_draw(self._h, pos, st.ctypes.data)
+        if vectors is None:
+            rc = lib().nmo_chain_draw(self._h, pos, st.ctypes.data)
+            return pos, st[0], rc
+        dv = DrawVectors()
+        for k in VECTOR_STATS:
+            vectors[k] = np.full(self.dim, np.nan)
+            setattr(dv, k, vectors[k].ctypes.data)
+        rc = lib().nmo_chain_draw_ex(self._h, pos, st.ctypes.data, C.byref(dv))
         return pos, st[0], rc
 
     def state(self):

@@ -6,7 +6,10 @@ reported here gets another seed in the test file's SEEDS / GENERIC_SEEDS / TAX_S
 The host-callback pass also reports a case whose trees stay below depth 3, an error-taxonomy case whose wall or fatal region is never met
 (or in which no chain is left to go on), and prints the oracle's wall time of every case.
 
-    python tools/small_chain_dry_run.py [--cus 256] [--only small|generic|hostcb]"""
+The vector-output pass (tests/test_gpu_vector_outputs.py) checks that every case's seed makes the events happen that the case is about, and
+looks for a seed where it does not.
+
+    python tools/small_chain_dry_run.py [--cus 256] [--only small|generic|hostcb|vectors]"""
 import argparse
 import ctypes as C
 import os
@@ -100,10 +103,39 @@ def hostcb():
     return len(cases), len(tax), bad
 
 
+def vectors():
+    """tests/test_gpu_vector_outputs.py: every case's oracle side with its committed seed must meet the case's conditions (a divergent leapfrog
+    from the initial point and one from elsewhere, a mass-matrix event after draw 0, a draw that stays and one that moves, both sides of the
+    end of tuning — less what the case drops by construction).  A case that does not is reported; its seeds 0 .. 31 are then run and the
+    first that does is printed (for the test file's SEEDS), or that there is none."""
+    import test_gpu_vector_outputs as V
+    bad, cases = [], V.all_cases()
+    for c in cases:
+        t = time.time()
+        first, why = None, []
+        for seed in ([c["seed"]] + [s for s in range(32) if s != c["seed"]]):
+            cc = dict(c, seed=seed)
+            o = V.oracle_side(O, cc)
+            why_s = (["an oracle chain failed"] if o["failed"] else []) + V.findings(cc, o["x0"], o["pos"], o["st"], o["vec"])
+            if seed == c["seed"]:
+                why = why_s
+                e = V.events(cc, o["x0"], o["pos"], o["st"], o["vec"])
+                note = (f"{int(e['div'].sum())} divergent draws ({int(e['div0'].sum())} from the initial point), {int(e['upd'][1:].sum())} mass-matrix events after "
+                        f"draw 0, {int(e['stay'].sum())} draws stay, {int(o['st']['n_steps'].sum())} leapfrogs, depth <= {int(o['st']['depth'].max())}")
+            if not why_s:
+                first = seed
+                break
+        print(f"  {c['id']} (seed {c['seed']}): {time.time() - t:.2f} s, {note}" + "".join("  <-- " + w for w in why)
+              + (f"  [first seed of 0 .. 31 that meets the conditions: {first}]" if why else ""))
+        if why:
+            bad.append(c["id"])
+    return len(cases), bad
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--cus", type=int, default=256)
-    ap.add_argument("--only", choices=["small", "generic", "hostcb"])
+    ap.add_argument("--only", choices=["small", "generic", "hostcb", "vectors"])
     a = ap.parse_args()
     O.lib()
     rc = 0
@@ -121,5 +153,10 @@ if __name__ == "__main__":
         t = time.time()
         n, n_tax, bad = hostcb()
         print(f"host-callback instantiations: {n} cases + {n_tax} error-taxonomy cases, {len(bad)} cases reported {bad}, {time.time() - t:.1f} s")
+        rc |= bool(bad)
+    if a.only in (None, "vectors"):
+        t = time.time()
+        n, bad = vectors()
+        print(f"vector outputs: {n} cases, {len(bad)} cases reported {bad}, {time.time() - t:.1f} s")
         rc |= bool(bad)
     sys.exit(rc)
