@@ -82,56 +82,8 @@ def needs_build():
 
 
 class StoreHazardError(RuntimeError):
-    """A translation unit's device assembly has a buffer store whose data registers are rewritten inside the hazard window."""
-
-
-def _scan_store_hazards(asm_path, what, allow_calls=True):
-    """tools/check_store_hazard.py's rule, both modes, on one unit's device assembly: the build fails on an unguarded
-    instance instead of leaving it to a parity suite that does not travel with a user's module build.  The rule lives in ONE place: the
-    tool is executed, not re-implemented (it ships in the repo next to this package; a wheel without tools/ skips the scan and says so)."""
-    tool = os.path.join(HERE, "..", "tools", "check_store_hazard.py")
-    if not os.path.exists(tool):
-        print(f"nuts_rs_amd.build: tools/check_store_hazard.py not found, {what} NOT scanned for store-data hazards", file=sys.stderr)
-        return
-    for mode in ([], ["--mubuf64"]):
-        r = subprocess.run([sys.executable, tool, asm_path] + mode, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise StoreHazardError(f"{what}: unguarded store-data hazard(s) in the generated assembly (python tools/check_store_hazard.py "
-                                   f"{' '.join(mode)}; guard the store as buf_store2 / LCtx::bst do, DESIGN §15):\n" + r.stdout[-3000:])
-    # DESIGN §22's rule as a scan: no out-of-line call inside a kernel that carries several chains per wavefront
-    tool2 = os.path.join(HERE, "..", "tools", "check_divergent_calls.py")
-    if os.path.exists(tool2):
-        r = subprocess.run([sys.executable, tool2, asm_path], capture_output=True, text=True)
-        if r.returncode != 0:
-            raise StoreHazardError(f"{what}: an out-of-line call inside a several-chains-per-wavefront kernel (python tools/check_divergent_calls.py; "
-                                   "force-inline the callee, DESIGN §22):\n" + r.stdout[-3000:])
-
-
-    # the software-managed VALU hazards (DPP / v_readlane / v_permlane*_swap / SGPR forwarding / transcendental results) at TEXT level: the
-    # compiler's hazard recogniser cannot see into an inline-asm instruction (DESIGN §22, incidents three and four)
-    tool3 = os.path.join(HERE, "..", "tools", "check_valu_hazards.py")
-    if os.path.exists(tool3):
-        r = subprocess.run([sys.executable, tool3, asm_path], capture_output=True, text=True)
-        if r.returncode != 0:
-            raise StoreHazardError(f"{what}: a software-managed VALU hazard without its wait states (python tools/check_valu_hazards.py):\n" + r.stdout[-3000:])
-
-
-    # the policy of §22's fourth incident as a scan: no out-of-line device call in the units of the small tilings (and in user modules of them)
-    if not allow_calls:
-        with open(asm_path) as f:
-            import re
-            n_calls, callees, last_sym = 0, set(), None
-            for line in f:
-                m = re.search(r"s_add_u32\s+s\d+,\s*s\d+,\s*([\w.$]+)@rel32@lo", line)
-                if m:
-                    last_sym = m.group(1)
-                if line.lstrip().startswith("s_swappc_b64"):
-                    n_calls += 1
-                    callees.add(last_sym or "?")
-        if n_calls:
-            raise StoreHazardError(f"{what}: {n_calls} out-of-line device call(s) (s_swappc_b64) to {sorted(callees)} in a unit that is built "
-                                   "without them (-DNM_DETMATH_INLINE=1; DESIGN §22): mark the callee(s) __forceinline__ (a __noinline__ helper in a "
-                                   "user density of a small tiling is not supported)")
+    """A finding of any rule of nuts_rs_amd/asm_scan.py but the exec-spill one: a buffer store whose data registers are rewritten inside the hazard
+    window, a call where the build allows none, a VALU hazard without its wait states."""
 
 
 class ExecSpillError(RuntimeError):
@@ -139,41 +91,71 @@ class ExecSpillError(RuntimeError):
     cause of the code-generation incidents of rounds 4 - 5) and the instance could not be repaired in the assembly."""
 
 
-def _repair_exec_spills(asm_path, cmd, what):
-    """tools/check_exec_spill.py on one unit's device assembly.  A finding is a miscompile of this toolchain (ROCm 7.2 hipcc: VGPR spill code
-    inserted between a join block's hoisted SGPR-to-lane spills and its `s_or_b64 exec, exec, s[..]`; on the edge that skips the `if` with
-    EXEC == 0 the spill stores nothing and the reload returns a stale slot).  The repair is done where the defect is: the exec restore is moved
-    up to the block's first instruction in the ASSEMBLY (everything it jumps over is exec-independent or one of the spill accesses it is
-    meant to cover), and the rest of the hipcc pipeline — assembler, lld, bundler, host compile — is replayed on the repaired file.  An
-    instance the tool cannot prove movable fails the build."""
+# what to tell the author of the code, by rule (asm_scan.py's ids; valu-A .. valu-G share a line)
+ADVICE = {
+    "exec-spill": "join block(s) with VGPR spill code before the exec restore (DESIGN §22; where not [fixable] in the assembly: perturb the source or "
+                  "build the unit with -mllvm -amdgpu-spill-sgpr-to-vgpr=false)",
+    "store-hazard": "unguarded store-data hazard(s) in the generated assembly (guard the store as buf_store2 / LCtx::bst do, DESIGN §15)",
+    "store-hazard-mubuf64": "unguarded store-data hazard(s), 64-bit MUBUF stores included (guard the store as buf_store2 / LCtx::bst do, DESIGN §15)",
+    "divergent-call": "out-of-line call(s) inside a several-chains-per-wavefront kernel (force-inline the callee, DESIGN §22)",
+    "valu": "software-managed VALU hazard(s) without their wait states (DESIGN §22)",
+    "device-call": "out-of-line device call(s) (s_swappc_b64) in a unit that is built without them (-DNM_DETMATH_INLINE=1; DESIGN §22): mark the callee(s) "
+                   "__forceinline__ (a __noinline__ helper in a user density of a small tiling is not supported)"}
+
+
+def _report(what, findings):
+    """The finding records as a message: per rule its advice and the first twenty records."""
+    out = []
+    for rule in dict.fromkeys(f["rule"] for f in findings):
+        fs = [f for f in findings if f["rule"] == rule]
+        out.append(f"{what}: {len(fs)} {ADVICE[rule[:4] if rule.startswith('valu-') else rule]}:")
+        out += [f"    {f['func']}: line {f['line']}: {f['text']}" + (f"   <- line {f['prod_line']}: {f['prod_text']}" if f["prod_line"] else "")
+                + (f"   (block {f['detail']['block']}{', [fixable]' * f['detail']['fixable']})" if f["detail"] else "") for f in fs[:20]]
+    return "\n".join(out)
+
+
+def _asm_scan(asm_path, allow_calls, fix=None):
+    """asm_scan.py on one device assembly -> its finding records.  ONE child interpreter, started by file path (it imports the standard library
+    only); a child, because the units are compiled from a thread pool and in-process scans of seconds each would queue on the interpreter lock.
+    The scanner is part of the package: no build goes without it, and a child that does not answer with records is an error."""
+    import json
+    args = [sys.executable, os.path.join(HERE, "asm_scan.py"), asm_path] + ([] if allow_calls else ["--no-calls"]) + (["--fix", fix] if fix else [])
+    r = subprocess.run(args, capture_output=True, text=True)
+    records = [json.loads(l) for l in r.stdout.splitlines()] if r.returncode in (0, 1) else []
+    if r.returncode != 0 and not records:
+        raise RuntimeError(f"the assembly scan did not run ({' '.join(args)}):\n" + r.stderr[-3000:])
+    return records
+
+
+def _replay(cmd, what):
+    """Re-run hipcc's own pipeline from the device assembler on (the commands `hipcc -###` shows for the same arguments): assembler, lld,
+    bundler, host compile.  For ONE offload architecture: with a second one the replay would assemble that one's unrepaired file as well."""
     import shlex
-    tool = os.path.join(HERE, "..", "tools", "check_exec_spill.py")
-    if not os.path.exists(tool):
-        print(f"nuts_rs_amd.build: tools/check_exec_spill.py not found, {what} NOT scanned for spills before an exec restore", file=sys.stderr)
-        return
-    r = subprocess.run([sys.executable, tool, asm_path], capture_output=True, text=True)
-    if r.returncode == 0:
-        return
-    fixed = asm_path + ".fixed"
-    r2 = subprocess.run([sys.executable, tool, asm_path, "--fix", fixed], capture_output=True, text=True)
-    if r2.returncode != 0:
-        raise ExecSpillError(f"{what}: VGPR spill code before the exec restore of a join block, not repairable in the assembly "
-                             f"(python tools/check_exec_spill.py; perturb the source or build the unit with -mllvm -amdgpu-spill-sgpr-to-vgpr=false):\n" + r2.stdout[-3000:])
-    print(f"nuts_rs_amd.build: {what}: repaired in the assembly:\n" + r.stdout[-1500:], file=sys.stderr)
-    os.replace(fixed, asm_path)
-    # replay the pipeline from the device assembler on (the commands hipcc itself ran: `hipcc -###` with the same arguments)
     plan = subprocess.run(cmd + ["-###"], capture_output=True, text=True).stderr.split("\n")
     steps = [shlex.split(l) for l in plan if l.lstrip().startswith('"')]
-    first = next((k for k, c in enumerate(steps) if "-cc1as" in c and "amdgcn-amd-amdhsa" in c), None)
-    if first is None:
-        raise ExecSpillError(f"{what}: cannot replay the compiler pipeline on the repaired assembly (no device assembler step in `hipcc -###`)")
-    for c in steps[first:]:
-        if "-E" in c and "-cc1" in c:          # (the host preprocessor step: its output is unchanged)
-            continue
-        subprocess.check_call(c)
-    r3 = subprocess.run([sys.executable, tool, asm_path], capture_output=True, text=True)
-    if r3.returncode != 0:
-        raise ExecSpillError(f"{what}: the repaired assembly still has a finding:\n" + r3.stdout[-2000:])
+    device_as = [k for k, c in enumerate(steps) if "-cc1as" in c and "amdgcn-amd-amdhsa" in c]
+    if len(device_as) != 1:
+        raise ExecSpillError(f"{what}: cannot replay the compiler pipeline on the repaired assembly: `hipcc -###` shows {len(device_as)} device assembler "
+                             "steps, and the replay is written for exactly one (a single --offload-arch)")
+    for c in steps[device_as[0]:]:
+        if not ("-E" in c and "-cc1" in c):          # (the host preprocessor step: its output is unchanged)
+            subprocess.check_call(c)
+
+
+def _scan_unit(asm_path, cmd, what, allow_calls=True):
+    """Every rule on one device assembly; a finding fails the build.  All but this: an exec-spill finding (a miscompile of ROCm 7.2's hipcc, DESIGN
+    §22) that asm_scan.py can prove movable is repaired where the defect is — the exec restore moves up to the block's first instruction in the
+    ASSEMBLY, the rest of hipcc's pipeline is replayed on the repaired file, and that file is scanned again."""
+    findings = _asm_scan(asm_path, allow_calls, fix=asm_path + ".fixed")
+    repaired = bool(findings) and all(f["detail"] and f["detail"]["fixable"] for f in findings)
+    if repaired:
+        print("nuts_rs_amd.build: repaired in the assembly:\n" + _report(what, findings), file=sys.stderr)
+        os.replace(asm_path + ".fixed", asm_path)
+        _replay(cmd, what)
+        findings = _asm_scan(asm_path, allow_calls)
+    if findings:          # (the message names all of them: a fixable spill beside another rule's finding is repaired once that one is gone)
+        stuck = any(f["detail"] and (repaired or not f["detail"]["fixable"]) for f in findings)
+        raise (ExecSpillError if stuck else StoreHazardError)(_report(what, findings))
 
 
 def _compile_scanned(hipcc, flags, src, out, what, link=False, allow_calls=True):
@@ -190,8 +172,7 @@ def _compile_scanned(hipcc, flags, src, out, what, link=False, allow_calls=True)
         if not asms and not src.endswith(".cpp"):
             raise RuntimeError(f"{what}: no device assembly among the compiler's temporaries (-save-temps=obj)")
         for a in asms:
-            _repair_exec_spills(a, cmd, what)
-            _scan_store_hazards(a, what, allow_calls)
+            _scan_unit(a, cmd, what, allow_calls)
         os.replace(prod, out)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
@@ -284,13 +265,13 @@ def build_density_module(header, struct_name, dim, out, dims_per_lane=0, waves_p
             raise ValueError("lane forms exist for dim <= 10")
         extra_flags = list(extra_flags) + [f"-DNM_MODULE_LANE_DENSITY={lane_struct}"]
     # The special functions (nm::dexp / dlog / dlog1p, merge_math, ...) are INLINED in a module of a several-chains-per-wavefront form (a user functor
-    # must not reach them through a call there: DESIGN §22, tools/check_divergent_calls.py) and, since round 5, in a module of a small tiling
+    # must not reach them through a call there: DESIGN §22, asm_scan.py's divergent-call rule) and, since round 5, in a module of a small tiling
     # (<= 4 doubles per lane) exactly as in the library's own units of those tilings: §22's fourth incident includes a dim-40 module whose
     # out-of-line build reported a wrong energy statistic while the inlined build of the same sources is bit-exact
     # (profiles/r05z_module_variants.txt), and a module is compiled on the USER's machine, where the engine's parity suite does not run.
     # Round 6: the defect behind those incidents is known (a VGPR spill placed above a join block's exec restore) and EVERY module
-    # build — whatever its tiling, with or without calls — is scanned for it and repaired in the assembly (_repair_exec_spills); the calls
-    # only made it likelier (SGPR spills around each call site).  The inlining rule stays as it was.
+    # build — whatever its tiling, with or without calls — is scanned for it and repaired in the assembly (_scan_unit: the rules are in the
+    # package, there is no build without them); the calls only made it likelier (SGPR spills around each call site).  The inlining rule stays.
     no_calls = bool(group_struct or lane_struct) or dpl <= 4
     if no_calls:
         extra_flags = list(extra_flags) + ["-DNM_DETMATH_INLINE=1"]

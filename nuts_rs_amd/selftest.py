@@ -16,7 +16,8 @@ every position and exact statistic; cases in selftest_cases.py).  `run_all()` ch
 (~0.1 - 0.3 s; sampler.ChainBatch calls it; NUTS_AMD_SELFTEST=0 turns it off).  The wrong-results incidents of rounds 4 - 5
 were all single instantiations that a compiler defect had hit while their siblings were right: the check is per instantiation.
 What this does NOT cover: the code of a user's density module (there is no oracle for a functor this repo has never seen) — a module is
-protected by the assembly scans of its build (nuts_rs_amd.build: tools/check_exec_spill.py names and repairs the defect itself)."""
+protected by the assembly scans of its build (nuts_rs_amd.build runs nuts_rs_amd/asm_scan.py on every module: its exec-spill rule names and
+repairs the defect itself)."""
 import json
 import os
 

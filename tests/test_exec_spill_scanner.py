@@ -56,6 +56,32 @@ def test_a_restore_that_cannot_be_moved_stays_an_error(tmp_path):
     assert _run(str(p), "--fix", str(tmp_path / "o.s")).returncode == 1
 
 
+@pytest.mark.parametrize("ins, movable", [("s_mov_b64 s[10:11], exec", False), ("s_mov_b32 s11, exec_lo", False), ("s_mov_b64 s[10:11], s[8:9]", True)])
+def test_a_restore_is_not_moved_above_an_instruction_that_reads_exec(tmp_path, ins, movable):
+    """An s_mov that READS exec between the label and the restore captures another value once the restore is moved above it: reported, not
+    repaired.  The same s_mov with an SGPR source does not depend on exec, and the finding stays repairable (the tightening stops there)."""
+    src = open(FIXTURE).read().replace("\tv_writelane_b32 v255, s65, 6\n", f"\tv_writelane_b32 v255, s65, 6\n\t{ins}\n", 1)
+    assert ins in src
+    p = tmp_path / "reads_exec.s"
+    p.write_text(src)
+    r = _run(str(p))
+    assert r.returncode == 1 and "block .LBB6_681: 11 exec-dependent spill access(es)" in r.stdout
+    assert ("[fixable]" in r.stdout) == movable
+    assert _run(str(p), "--fix", str(tmp_path / "o.s")).returncode == (0 if movable else 1)
+
+
+def test_the_replay_refuses_a_plan_with_two_device_assembler_steps(tmp_path):
+    """The replay re-runs everything from THE device assembler step on; with a second offload architecture it would assemble that one's
+    unrepaired file over the result, so a plan that shows two such steps is refused (a stub in hipcc's place prints the plan; nothing is compiled)."""
+    from nuts_rs_amd import build as B
+    step = ' "/opt/rocm/lib/llvm/bin/clang" "-cc1as" "-triple" "amdgcn-amd-amdhsa" "-target-cpu" "{}" "-o" "/dev/null" "t.s"'
+    stub = tmp_path / "hipcc_stub"
+    stub.write_text("#!/bin/sh\ncat >&2 <<'EOF'\nclang version 0\n" + step.format("gfx942") + "\n" + step.format("gfx950") + "\nEOF\n")
+    stub.chmod(0o755)
+    with pytest.raises(B.ExecSpillError, match="2 device assembler steps"):
+        B._replay([str(stub), "-c", "t.hip"], "stub unit")
+
+
 def test_spills_after_the_restore_or_in_blocks_not_entered_with_exec_zero_are_fine(tmp_path):
     ok = ("f:\n\ts_and_saveexec_b64 s[4:5], vcc\n\ts_cbranch_execz .LBB0_2\n\tv_mov_b32_e32 v0, 1\n.LBB0_2:\n\ts_or_b64 exec, exec, s[4:5]\n"
           "\tscratch_store_dword off, v0, off offset:4 ; 4-byte Folded Spill\n\ts_endpgm\n.Lfunc_end0:\n")
@@ -71,7 +97,7 @@ def test_spills_after_the_restore_or_in_blocks_not_entered_with_exec_zero_are_fi
 
 @pytest.mark.skipif(not os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")), reason="needs hipcc")
 def test_the_build_repairs_a_finding_and_replays_the_compiler_pipeline(tmp_path):
-    """nuts_rs_amd.build._repair_exec_spills end to end, without a GPU: a small kernel's device assembly gets the defect's shape injected (SGPR-to-lane
+    """nuts_rs_amd.build._scan_unit end to end, without a GPU: a small kernel's device assembly gets the defect's shape injected (SGPR-to-lane
     spill, VGPR spill, THEN the exec restore in a block entered by s_cbranch_execz); the build's hook must flag it, move the restore, re-run hipcc's own
     assembler / lld / bundler / host steps, and the OBJECT that comes out must carry the repaired order."""
     from nuts_rs_amd import build as B
@@ -90,7 +116,7 @@ def test_the_build_repairs_a_finding_and_replays_the_compiler_pipeline(tmp_path)
     assert text.count(f"{label}:\n") == 1
     asm.write_text(text.replace(f"{label}:\n", inject))
     assert _run(str(asm)).returncode == 1                                       # the injected shape is a finding
-    B._repair_exec_spills(str(asm), cmd, "test kernel")
+    B._scan_unit(str(asm), cmd, "test kernel")
     assert _run(str(asm)).returncode == 0
     # the object hipcc's replayed pipeline produced: its device code has the restore in front of the spill store
     llvm = "/opt/rocm/lib/llvm/bin"

@@ -2,7 +2,7 @@
 """A tuning build of some translation units with extra flags, linked with the regular objects of the others:
     python tools/build_variant.py <tag> "<extra flags>" unit[@variant] [unit[@variant] ...]
 -> nuts_rs_amd/libnuts_amd_<tag>.so (run a tool with NUTS_AMD_LIB=<that file>).  The units go through the same compile path as the regular
-build (assembly scans, exec-spill repair: nuts_rs_amd.build._compile_scanned) with their variant's flags (@small / @large / @inl)."""
+build (nuts_rs_amd.build._compile_scanned: assembly scan, exec-spill repair) with their variant's flags (@small / @large / @inl)."""
 import os
 import subprocess
 import sys
